@@ -16,15 +16,24 @@ row blocks dealt in cyclic groups (each GPU stores only the lower tiles of its o
 its rows, and the exchange is device-initiated: a finished tile is stored by the task that
 produced it straight into the windows of the ranks that read it (IPC-mapped over xGMI), the
 diagonal-block inverses likewise into every rank (gpr_amd/csrc/gprx_dist.cpp; strong scaling:
-value = fits/s of the job).  The same run also measures --mode replicas (every rank fits its
+value = fits/s of the job).  A --full run also measures --mode replicas (every rank fits its
 own GP, weak scaling) and reports it under "replicas"; `--mode replicas` makes that the
 headline.  Predict is query-sharded over the ranks (X and alpha replicated).
 
-The other BASELINE.json configurations are measured in the same run ("configs" in the JSON
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what the headline needs and no
+more: it sets up, runs W untimed fits, times K fits, and prints the line.  `--dump-outputs DIR`
+also writes what the last timed fit returned (DIR/alpha.npy, logdet.npy, datafit.npy; float64),
+so two builds can be compared output for output: the inputs are the same in every run.
+
+`--full` adds every other measurement to the same run and line: predict, posterior variance,
+LML + gradient and the covariance build on the headline model, the replicas figure beside a
+sharded headline and the per-rank traced fit, the CPU baselines, the rooflines' figures from
+the committed profiles, and the other BASELINE.json configurations ("configs" in the JSON
 line, --configs 0 skips them), each with its own dominant-kernel roofline and a labelled CPU
 baseline: C2 (N=4096 d=16 Gaussian fp64, replicas), C4 (N=32768 d=32 RationalQuadratic fp32 with
 the fp64 refinement; sharded over the ranks for N > 1, its BASELINE form), C5 (sparse GP M=2048
-inducing, N=1e6 d=64 fp64, dense rows sharded over the ranks).
+inducing, N=1e6 d=64 fp64, dense rows sharded over the ranks).  The options that size or select
+those parts (--legs, --predict-q, --cpu-n, ...) act under --full only.
 
 Prints ONE JSON line on rank 0 (plus human-readable detail on stderr).
 """
@@ -662,6 +671,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (predict, variance, LML + gradient, build, "
+                         "the replicas figure and per-rank traced fit for N > 1, configs C2/C4/C5, CPU baselines, "
+                         "figures from the committed profiles); the options below that size or select those "
+                         "parts act under --full only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed fit returned as DIR/<name>.npy "
+                         "(alpha, logdet, datafit; float64)")
     ap.add_argument("--n", "--ntrain", dest="n", type=int, default=None,
                     help="training points (--ntrain under torch.distributed.run, whose parser takes --n)")
     ap.add_argument("--d", type=int, default=None)
@@ -692,10 +709,22 @@ def main():
     legs = None if args.legs == "all" else set(args.legs.split(","))
     if legs is not None and not legs <= set(LEGS):
         ap.error(f"unknown legs {sorted(legs - set(LEGS))}")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        # a plain run: the headline's timed fits alone
+        if legs is not None:
+            ap.error("--legs selects among the parts of a --full run: pass --full with it")
+        legs = {"c3"}
+        args.predict_q = args.variance_q = args.lml = args.build_iters = args.configs = args.dist_lml = 0
+        args.cpu_n = args.cpu_predict_q = 0
+        args.cpu_lml_ns = ""
 
     def want(leg):
         return legs is None or leg in legs
 
+    if args.dump_outputs and not want("c3"):
+        ap.error("--dump-outputs writes the headline fit's outputs: --legs must include c3")
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
     env_world = os.environ.get("WORLD_SIZE")
@@ -772,10 +801,14 @@ def main():
             dmodel = make_model(dctx)
             el, infos, st = timed_fits(dmodel, dctx, gpr_amd.gprx.FIT_DISTRIBUTED)
             dres = {"elapsed": el, "infos": infos}
+            if args.dump_outputs and rank == 0:  # (a local read: the rank's copy of alpha)
+                dres["alpha"] = dmodel.alpha()
             # per-rank evidence for reading a scaling curve: after the timed
-            # fits, one more traced fit (untimed) for the measured chain step
+            # fits, one more traced fit (untimed) for the measured chain step (--full); a plain
+            # run records the rank's identity alone
             try:
-                dres["rank_rec"] = dist_rank_record(dctx, dmodel, transport)
+                dres["rank_rec"] = (dist_rank_record(dctx, dmodel, transport) if args.full
+                                    else dict(dctx.info(), transport_bench=transport))
             except Exception as e:
                 dres["rank_rec"] = {"rank": rank, "error": repr(e)}
             if args.dist_lml:  # LML + gradient on the sharded factor (row-block partials, one all-reduce)
@@ -792,14 +825,20 @@ def main():
     # ---- one independent fit per GPU (the N = 1 headline; the replicas extra for N > 1) -----
     ctx = gpr_amd.Context(local_rank)
     model = make_model(ctx)
-    if want("c3"):
+    # (a plain run whose headline is the sharded fit above leaves the replicas out)
+    # (the ranks agree that the sharded fit ran everywhere)
+    plain_dist = (not args.full and args.mode == "dist" and (world > 1 or args.force_dist)
+                  and (dres is not None if dist is None else dist.min(1.0 if dres is not None else 0.0) > 0))
+    if want("c3") and not plain_dist:
         el_r, infos_r, stats = timed_fits(model, ctx)
+        alpha_r = model.alpha() if args.dump_outputs and rank == 0 else None  # (before any other leg refits)
         replicas = {"value": world * args.steps / el_r, "ms_per_step": 1e3 * el_r / args.steps,
                     "scaling": "weak", "fits_per_step": world}
     else:  # a profiling pass of another leg: one untimed fit for predict / variance
         if want("predict") or want("variance"):
             model.fit()
         el_r, infos_r, stats, replicas = None, [], {}, {"value": None, "ms_per_step": None}
+        alpha_r = None
 
     headline_dist = dres is not None and args.mode == "dist" and (world > 1 or args.force_dist)
     if headline_dist:
@@ -807,6 +846,15 @@ def main():
         ms_per_step = 1e3 * dres["elapsed"] / args.steps
     else:
         value, ms_per_step = replicas["value"], replicas["ms_per_step"]
+
+    # --dump-outputs: what the headline's last timed fit returned to its caller (rank 0's copy):
+    # the regression vectors and the fit's log-determinant and data-fit term
+    if args.dump_outputs and rank == 0:
+        last = (dres["infos"] if headline_dist else infos_r)[-1]
+        alpha_out = dres["alpha"] if headline_dist else alpha_r
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("alpha", alpha_out), ("logdet", [last.logdet]), ("datafit", [last.datafit])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
 
     # prediction throughput, query-sharded over the ranks (X and alpha replicated): each rank
     # predicts its contiguous slice of the Q queries; device time of the fused predict
@@ -987,7 +1035,7 @@ def main():
               for k, v in stats.items()}
     g_roof = world if headline_dist else 1
     t_roof = fit_roofline_ms(n, d, m, g_roof)
-    traffic = traffic_from_profile() if not headline_dist else None
+    traffic = traffic_from_profile() if args.full and not headline_dist else None
     fit_ms = float(np.median([i.ms_build + i.ms_factor + i.ms_solve for i in infos])) if infos else None
 
     # every rank's identity and exchange figures (rank 0 prints them): ranks_seen counts the
@@ -1025,6 +1073,8 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
+            "outputs_dumped": args.dump_outputs,
             "ms_per_step": ms_per_step,
             "higher_is_better": True,
             "scaling": "strong" if headline_dist else "weak",
@@ -1052,12 +1102,12 @@ def main():
                          # its matrix-pipe busy fraction from the committed PMC pass
                          "rocprof": (rocprof_from_profile("c3", ("potrf_tiles_kernel<double, false>",),
                                                           1e3 * avg_ms if avg_ms else None)
-                                     if not headline_dist else None),
+                                     if args.full and not headline_dist else None),
                          "mfma_busy": (mfma_from_profile("c3", ("potrf_tiles_kernel<double, false>",))
-                                       if not headline_dist else None)},
+                                       if args.full and not headline_dist else None)},
             "fit_roofline": {"t_roof_ms": t_roof, "gpus": g_roof, "t_fit_device_ms": fit_ms,
                              "frac": t_roof / fit_ms if fit_ms else None},
-            "replicas": replicas if world > 1 else None,
+            "replicas": replicas if world > 1 and not plain_dist else None,
             "dist_error": dist_error,
             "dist_transport": transport,
             # N > 1: how many ranks took part, on how many GPUs, and per rank its device, transport,

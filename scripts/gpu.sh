@@ -9,8 +9,8 @@
 #   tests      the whole `pytest -m gpu` suite (GPU_TESTS="tests/test_x.py ..." selects files,
 #              GPU_K="expr" a -k filter)
 #   smoke      __graft_entry__.smoke()
-#   bench      the default bench line (-> bench.json; extra args in BENCH_ARGS)
-#   profile    one `rocprofv3 --kernel-trace --stats` pass per bench leg (bench.py --legs L), then
+#   bench      the --full bench line (-> bench.json; extra args in BENCH_ARGS)
+#   profile    one `rocprofv3 --kernel-trace --stats` pass per bench leg (bench.py --full --legs L), then
 #              the PMC passes: FETCH_SIZE and WRITE_SIZE of the C3 fit and of the path-0 build,
 #              the MFMA-busy counters of the C3 and C4 factorisations.  scripts/profile_collect.py
 #              TAG turns the output into the profiles/TAG_<leg>_* summaries bench.py attaches.
@@ -38,7 +38,7 @@ fail() { echo "step $1 failed (rc $2)"; tail -n 30 "$3" 2>/dev/null; exit "$2"; 
 prof_leg() {  # $1 = leg: kernel trace + stats of one bench leg in its own process
     local leg=$1
     (cd /tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_$leg" -o "$leg" \
-        -- python3 "$R/bench.py" --legs "$leg" --cpu-n 0 --cpu-lml-ns "" --cpu-predict-q 0 > "$O/prof_$leg.json" 2> "$O/prof_$leg.err") \
+        -- python3 "$R/bench.py" --full --legs "$leg" --cpu-n 0 --cpu-lml-ns "" --cpu-predict-q 0 > "$O/prof_$leg.json" 2> "$O/prof_$leg.err") \
         || fail "profile:$leg" $? "$O/prof_$leg.err"
     echo "profile $leg ok"
 }
@@ -47,7 +47,7 @@ pmc_leg() {  # $1 = leg, $2 = output name, $3.. = counters (one block-limited pa
     local leg=$1 name=$2
     shift 2
     (cd /tmp && timeout -s KILL 240 rocprofv3 --pmc "$@" --output-format csv -d "$O/$name" -o "$name" \
-        -- python3 "$R/bench.py" --legs "$leg" --cpu-n 0 --cpu-lml-ns "" --cpu-predict-q 0 --steps 2 --warmup 1 --build-iters 2 \
+        -- python3 "$R/bench.py" --full --legs "$leg" --cpu-n 0 --cpu-lml-ns "" --cpu-predict-q 0 --steps 2 --warmup 1 --build-iters 2 \
         > "$O/$name.json" 2> "$O/$name.err") || fail "pmc:$name" $? "$O/$name.err"
     echo "pmc $name ok"
 }
@@ -65,7 +65,7 @@ for step in "$@"; do
         tail -n 2 "$O/smoke.log"
         ;;
     bench)
-        timeout -k 10 600 python -u bench.py $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" \
+        timeout -k 10 600 python -u bench.py --full $BENCH_ARGS > "$O/bench.json" 2> "$O/bench.err" \
             || fail bench $? "$O/bench.err"
         python scripts/bench_brief.py "$O/bench.json"
         ;;
@@ -86,13 +86,13 @@ for step in "$@"; do
         ;;
     shared)
         GPRX_DIST_SHARED_GPU=1 timeout -k 10 500 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-            --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 100)) bench.py --gpus 2 \
+            --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 100)) bench.py --gpus 2 --full \
             > "$O/shared_bench.json" 2> "$O/shared_bench.err" || fail shared $? "$O/shared_bench.err"
         python scripts/bench_brief.py "$O/shared_bench.json"
         ;;
-    spawn)  # the driver's N > 1 command as it is (bench.py --gpus N, no launcher, default legs),
+    spawn)  # the driver's N > 1 command as it is (bench.py --gpus N --full, no launcher, default legs),
             # rehearsed with SPAWN_N (default 2) ranks sharing this one GPU
-        GPRX_DIST_SHARED_GPU=1 timeout -k 10 900 python bench.py --gpus ${SPAWN_N:-2} $SPAWN_ARGS \
+        GPRX_DIST_SHARED_GPU=1 timeout -k 10 900 python bench.py --gpus ${SPAWN_N:-2} --full $SPAWN_ARGS \
             > "$O/spawn_bench.json" 2> "$O/spawn_bench.err" || fail spawn $? "$O/spawn_bench.err"
         python scripts/bench_brief.py "$O/spawn_bench.json"
         ;;
@@ -123,7 +123,7 @@ for step in "$@"; do
         ;;
     ab)
         shopt -s nullglob
-        Q="--cpu-n 0 --cpu-predict-q 0 --legs c3 --steps 20 $AB_ARGS"
+        Q="--full --cpu-n 0 --cpu-predict-q 0 --legs c3 --steps 20 $AB_ARGS"
         for rep in 1 2; do
             for f in tools/ab/*.so; do
                 b=$(basename "$f" .so)
@@ -145,7 +145,7 @@ for step in "$@"; do
             || fail distab $? "$O/distab.err"
         ;;
     envab)
-        Q="--cpu-n 0 --cpu-predict-q 0 --legs c3 --steps 20 $AB_ARGS"
+        Q="--full --cpu-n 0 --cpu-predict-q 0 --legs c3 --steps 20 $AB_ARGS"
         for rep in 1 2; do
             for v in $AB_ENVS; do
                 b=$(echo "$v" | tr '=/' '__')

@@ -1,11 +1,15 @@
 """bench.py's process contract on the CPU (no GPU here): `--gpus N` with no launcher starts N
 ranks itself and fails as a whole when a rank fails; a launcher's WORLD_SIZE must agree with
 --gpus.  The GPU form (two spawned ranks sharing one GPU) is
-tests/test_gpu_dist.py::test_bench_spawns_ranks_without_launcher."""
+tests/test_gpu_dist.py::test_bench_spawns_ranks_without_launcher.  Plain and --full runs: --legs
+belongs to --full; a plain run on the GPU measures the headline alone and --dump-outputs writes
+its outputs."""
 import os
 import subprocess
 import sys
 import time
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 QUICK = ["--steps", "1", "--warmup", "0", "--ntrain", "256", "--configs", "0", "--lml", "0", "--build-iters", "0",
@@ -32,3 +36,52 @@ def test_spawned_ranks_fail_together_without_gpu():
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert time.monotonic() - t0 < 240
+
+
+def test_legs_need_full():
+    """--legs selects among the parts of a --full run; a plain run refuses it (argument error,
+    before any library is loaded) instead of silently measuring the headline alone."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--legs", "predict"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2
+    assert "--full" in r.stderr
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--full", "--legs", "predict",
+                        "--dump-outputs", "unused"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2
+    assert "c3" in r.stderr
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run times exactly --steps fits and nothing else (every other part of the line is
+    null), and --dump-outputs writes what the last timed fit returned: alpha (against the oracle,
+    at the suite's fp64 tolerance), the log-determinant and the data-fit term y^T alpha."""
+    import json
+
+    import numpy as np
+
+    from gpr_amd.synth import C3, make_data
+    from oracle import oracle as O
+    from tests.helpers import TOL, relerr
+    n, d = 1000, 8
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--ntrain", str(n), "--d", str(d), "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and not line["full"]
+    assert line["ms_per_step"] > 0 and abs(line["value"] * line["ms_per_step"] - 1e3) <= 1e-6 * 1e3
+    for k in ("predict", "variance", "lml_grad", "build", "cpu_baseline", "configs"):
+        assert line[k] is None, k
+    assert sorted(p.name for p in out.iterdir()) == ["alpha.npy", "datafit.npy", "logdet.npy"]
+    alpha, logdet, datafit = (np.load(out / f"{k}.npy") for k in ("alpha", "logdet", "datafit"))
+    assert alpha.dtype == np.float64 and alpha.shape == (n, C3["m"])
+    assert logdet.dtype == datafit.dtype == np.float64 and logdet.shape == datafit.shape == (1,)
+    X, Y = make_data(n, d, C3["m"])
+    a_ref, _ = O.fit(C3["kernel"], X, Y, C3["sigma"])
+    assert relerr(alpha, a_ref) <= TOL[np.dtype(np.float64)]
+    assert np.isfinite(logdet[0])
+    assert abs(datafit[0] - float(np.sum(Y * alpha))) <= 1e-9 * abs(datafit[0])

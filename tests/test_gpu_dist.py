@@ -835,7 +835,7 @@ def test_bench_two_processes_rccl_fallback(tmp_path):
         port = str(so.getsockname()[1])
     env = dict(os.environ, GPRX_DIST_SHARED_GPU="1", GPRX_RCCL_FAIL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
-           "127.0.0.1", "--master-port", port, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
+           "127.0.0.1", "--master-port", port, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "2",
            "--warmup", "1", "--ntrain", "2048", "--configs", "0", "--lml", "0", "--build-iters", "0", "--cpu-n", "0",
            "--predict-q", "256", "--variance-q", "0", "--cpu-lml-ns", "", "--cpu-predict-q", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
@@ -864,7 +864,7 @@ def test_bench_spawns_ranks_without_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["GPRX_DIST_SHARED_GPU"] = "1"
     env["GPRX_BENCH_TIMEOUT_S"] = "280"
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--steps", "2", "--warmup", "1",
            "--configs", "0", "--ntrain", "4096", "--lml", "0", "--build-iters", "0", "--cpu-n", "0",
            "--predict-q", "256", "--variance-q", "0", "--cpu-lml-ns", "", "--cpu-predict-q", "0"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300, cwd=root)
