@@ -42,9 +42,14 @@ template <typename T>
 void launch_sym_fill(T* C, int64_t ldc, int64_t n, hipStream_t s);
 template <typename T>
 void launch_sum_partials(T* S, int64_t stride, int P, hipStream_t s);
+// (k_append.hip) S (lower tiles, n x n, lds) += the P split-K partials (n x n each), in order
+template <typename T>
+void launch_schur_sum(T* S, int64_t lds, const T* part, int64_t n, int P, hipStream_t s);
 
 gprx_status gprx_dev_bench_impl(gprx_dtype dtype, int32_t what, int64_t M, int64_t N, int64_t K, int32_t iters,
                                 double* ms, Exec* ex);
+gprx_status gprx_dev_forward_panel_impl(gprx_dtype dtype, const void* L, int64_t n, void* R, int32_t rows,
+                                        int32_t use_gemm, Exec* ex, hipStream_t s);
 
 static thread_local std::string t_last_error;
 thread_local Prof* g_prof = nullptr;
@@ -314,6 +319,9 @@ struct gprx_model {
     // across calls -- at Q = 65536, N = 16384 one buffer is 8.6 GB, whose hipMalloc + free per
     // call cost more than the solve on some boxes
     DevBuf pvRa, pvRb, pvFq;  // (+ the queries' pair features)
+    // gprx_model_append workspace: the new rows' panel, the sin/cos tables of the sample ranges it
+    // builds from, the old partial block (restored when the update is refused) and the new alpha
+    DevBuf apPanel, apTab, apStash, apAlpha, apPart;  // (+ the Schur update's split-K partials)
     // a refit, an LML call or new data frees that workspace when it is large (one
     // big variance call must not leave too little HBM for the next fit on the device)
     void trim_posterior_workspace() {
@@ -331,6 +339,7 @@ struct gprx_model {
     // LU fallback state (k_getrf.hip), double for both scalar types: the factored matrix,
     // pivots, the 128-block inverses of L and U, and scratch
     int method = 0;  // factor of the current fit: 0 Cholesky (A, Linv), 1 LU (lu, ipiv, luL, luU)
+    bool lu_forced = false;  // ... asked for by GPRX_FIT_FORCE_LU (gprx_model_append refits the same way)
     DevBuf lu, ipiv, luUt, luB, lured;
     double lu_sign = 1;  // sign of det(K + sigma^2 I) from the LU
     // distributed fit (gprx_dist.cpp): the engine (per-rank buffers, schedules) and whether
@@ -847,6 +856,7 @@ static gprx_status model_fit(gprx_model* M, uint32_t flags, gprx_fit_info* out) 
                  "gprx_model_fit: GPRX_FIT_DISTRIBUTED needs a context from gprx_ctx_create_dist / _peer");
     // the SVD inversion methods' stand-in: the LU in double directly.  On a distributed
     // context every rank runs it on its replicated X, Y (as the NOT_SPD fallback below)
+    M->lu_forced = (flags & GPRX_FIT_FORCE_LU) != 0;
     if (flags & GPRX_FIT_FORCE_LU) {
         lu_fit_replicated<T>(M, out);
         return GPRX_OK;
@@ -1100,6 +1110,240 @@ static void solve_rows_for(gprx_model* M, const T* dXq, const T* dtabQ, int64_t 
                          M->flag.as<int>(), s);
     }
     trsm_rows<T>(M->A.as<T>(), M->ld, M->np, M->Linv.as<T>(), R, qp, qp, s);
+}
+
+// ---------------------------------------------------------------------------------------
+// gprx_model_append: AddSample x k + Initialize (lib/GaussianProcess.cpp:36-51, 118-130) by
+// extending the Cholesky factor instead of refitting.  With n0 the last full 128-block boundary
+// below n, rows [0, n0) of L do not depend on later rows and are kept; the t = n - n0 rows of
+// the old partial block and the k new samples (the "active" rows) are redone, so the identity
+// padding stays at the end of the factor:
+//   panel   P = L[n0.., 0..n0): the old tail's rows are in A, the new rows are
+//           K(Xnew, X[0:n0]) L00^{-T} (one chained panel launch, k_append.hip, or trsm_rows);
+//   block   S = K(act, act) + s^2 I - P P^T, identity-padded to 128, factored in place
+//           (its diagonal-block inverses into Linv);
+//   labels  z = L^{-1} Y for ALL rows against the whole new factor (the label rows found in A
+//           are not reused: refine_f32 leaves residuals there), alpha by the chained back
+//           substitution, log det and data fit by the fit's reductions over all n + k rows.
+// Nothing the fitted model reads is replaced before the status words are known: a grown
+// factor is built in new buffers (one O(N^2) copy per 128 appended rows), an update inside
+// the existing padding stashes the 128 x 128 partial block and its inverse and restores them
+// (and the zero panel rows) when the update is refused; alpha is solved into a second buffer.
+// ---------------------------------------------------------------------------------------
+static void swap_buf(DevBuf& a, DevBuf& b) {
+    std::swap(a.p, b.p);
+    std::swap(a.bytes, b.bytes);
+}
+
+// b grown to at least `need` bytes, its first `keep` bytes kept (with head-room: a run of
+// one-row appends reallocates rarely)
+static void grow_keep(DevBuf& b, size_t need, size_t keep, hipStream_t s) {
+    if (need <= b.bytes && b.p) return;
+    DevBuf nb;
+    nb.ensure(need + need / 8 + 4096);
+    GPRX_HIP(hipStreamSynchronize(s));
+    if (keep && b.p) GPRX_HIP(hipMemcpy(nb.p, b.p, std::min(keep, b.bytes), hipMemcpyDeviceToDevice));
+    swap_buf(b, nb);
+}
+
+template <typename T>
+static gprx_status model_append(gprx_model* M, const void* Xnew, const void* Ynew, int64_t k, uint32_t flags,
+                                gprx_fit_info* out) {
+    gprx_ctx* ctx = M->ctx;
+    GPRX_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const KCanon<T>& K = kcanon<T>(M);
+    const int d = M->d, m = M->m;
+    const int64_t n = M->n, n1 = n + k;
+    const uint32_t fit_flags = flags & (GPRX_FIT_NO_LU_FALLBACK | GPRX_FIT_F32_NO_REFINE);
+    M->trim_posterior_workspace();
+    // the new rows behind the old ones (row-major: contiguous); nothing reads them before n is
+    // published.  Host or device memory, as gprx_model_set_data.
+    grow_keep(M->X, sizeof(T) * n1 * d, sizeof(T) * n * d, s);
+    grow_keep(M->Y, sizeof(T) * n1 * m, sizeof(T) * n * m, s);
+    GPRX_HIP(hipStreamSynchronize(s));
+    GPRX_HIP(hipMemcpy(M->X.as<T>() + n * d, Xnew, sizeof(T) * k * d, hipMemcpyDefault));
+    GPRX_HIP(hipMemcpy(M->Y.as<T>() + n * m, Ynew, sizeof(T) * k * m, hipMemcpyDefault));
+    // full refit of the extended data: the factor is the LU (a forced LU stays one), or the
+    // trailing Cholesky below met a non-positive pivot
+    auto refit = [&](uint32_t f) {
+        M->n = n1;
+        M->fitted = M->has_alpha = M->inv_ready = false;
+        return model_fit<T>(M, f, out);
+    };
+    if (M->method == 1 || M->dist_fitted) return refit(fit_flags | (M->method == 1 && M->lu_forced ? GPRX_FIT_FORCE_LU : 0u));
+
+    const int64_t np = M->np, mp = M->mp;
+    const int64_t n0 = n / DB * DB, t = n - n0, na = t + k, np1 = round_up(n1, (int64_t)DB), nap = np1 - n0;
+    const bool relay = np1 > np;  // the padding is used up: A, Linv re-laid (never the inverse rows of a want_inv fit)
+    const int64_t ld0 = M->ld, ld1 = relay ? np1 + mp : ld0;
+    const bool gemm = (flags & GPRX_APPEND_SOLVE_GEMM) != 0;
+    const bool gemm_new = gemm || k > DB;  // the new rows' panel: chained kernel up to 128 rows
+    DevBuf newA, newLinv;
+    T *A1, *Li1;
+    if (relay) {
+        newA.ensure(sizeof(T) * ld1 * np1);
+        newLinv.ensure(sizeof(T) * np1 * DB);
+        A1 = newA.as<T>();
+        Li1 = newLinv.as<T>();
+        GPRX_HIP(hipMemset2DAsync(A1 + np, sizeof(T) * ld1, 0, sizeof(T) * (ld1 - np), np, s));
+        GPRX_HIP(hipMemsetAsync(A1 + np * ld1, 0, sizeof(T) * ld1 * (np1 - np), s));
+        GPRX_HIP(hipMemcpy2DAsync(A1, sizeof(T) * ld1, M->A.p, sizeof(T) * ld0, sizeof(T) * np, np,
+                                  hipMemcpyDeviceToDevice, s));
+        GPRX_HIP(hipMemcpyAsync(Li1, M->Linv.p, sizeof(T) * np * DB, hipMemcpyDeviceToDevice, s));
+    } else {  // (then t > 0: the partial block is the last one, n0 = np - 128)
+        A1 = M->A.as<T>();
+        Li1 = M->Linv.as<T>();
+        M->apStash.ensure(2 * sizeof(T) * DB * DB);
+        T* st = M->apStash.as<T>();
+        GPRX_HIP(hipMemcpy2DAsync(st, sizeof(T) * DB, A1 + n0 + n0 * ld1, sizeof(T) * ld1, sizeof(T) * DB, DB,
+                                  hipMemcpyDeviceToDevice, s));
+        GPRX_HIP(hipMemcpyAsync(st + DB * DB, Li1 + n0 * DB, sizeof(T) * DB * DB, hipMemcpyDeviceToDevice, s));
+        if (n0 > 0) GPRX_HIP(hipMemset2DAsync(A1 + n, sizeof(T) * ld1, 0, sizeof(T) * (np1 - n), n0, s));
+    }
+    auto restore = [&]() {  // the fitted model as it was (an update inside the padding wrote into A, Linv)
+        if (relay) return;
+        T* st = M->apStash.as<T>();
+        GPRX_HIP(hipMemcpy2DAsync(A1 + n0 + n0 * ld1, sizeof(T) * ld1, st, sizeof(T) * DB, sizeof(T) * DB, DB,
+                                  hipMemcpyDeviceToDevice, s));
+        GPRX_HIP(hipMemcpyAsync(Li1 + n0 * DB, st + DB * DB, sizeof(T) * DB * DB, hipMemcpyDeviceToDevice, s));
+        if (n0 > 0) GPRX_HIP(hipMemset2DAsync(A1 + n, sizeof(T) * ld1, 0, sizeof(T) * (np1 - n), n0, s));
+        GPRX_HIP(hipStreamSynchronize(s));
+    };
+    M->info.ensure(sizeof(int));
+    M->flag.ensure(sizeof(int));
+    M->red.ensure(sizeof(double) * (2 + 2 * (np1 / GT + 1)));
+    M->apAlpha.ensure(sizeof(T) * np1 * m);
+    launch_fit_status_init(M->info.as<int>(), M->flag.as<int>(), s);
+    const T sig = (T)M->sigma;
+    const T sigma2 = sig * sig;
+    const T* Xall = M->X.as<T>();
+    const T* Xact = Xall + n0 * d;
+    const T* Xn = Xall + n * d;
+    static const bool direct = std::getenv("GPRX_PREDICT") && std::string(std::getenv("GPRX_PREDICT")) == "direct";
+    // the cross rows as MFMA pair statistics under solve_rows_for's conditions (fp64 only)
+    const bool cross_mma = std::is_same<T, double>::value && !direct && pairs_mma_supported<T>(K, 1);
+    GPRX_HIP(hipEventRecord(ctx->ev[0], s));
+    // sin/cos tables of the sample ranges the builds read (a table's planes are n x d of ITS range)
+    T *tabAct = nullptr, *tabNew = nullptr, *tabLead = nullptr;
+    if (K.nper > 0) {
+        const int64_t pl = 2 * K.nper * (int64_t)d;
+        const bool lead = n0 > 0 && !cross_mma;
+        M->apTab.ensure(sizeof(T) * pl * (na + k + (lead ? n0 : 0)));
+        tabAct = M->apTab.as<T>();
+        launch_sincos_tables<T>(K, Xact, na, d, tabAct, s);
+        if (lead) {  // the VALU cross build's two sides
+            tabNew = tabAct + pl * na;
+            tabLead = tabNew + pl * k;
+            launch_sincos_tables<T>(K, Xn, k, d, tabNew, s);
+            launch_sincos_tables<T>(K, Xall, n0, d, tabLead, s);
+        }
+    }
+    const int64_t ldp = round_up(k, (int64_t)GT);
+    T* P = nullptr;
+    if (n0 > 0) {  // K(Xnew, X[0:n0]) into the panel buffer (k x n0, zero rows up to ldp)
+        M->apPanel.ensure(sizeof(T) * ldp * n0);
+        P = M->apPanel.as<T>();
+        GPRX_HIP(hipMemsetAsync(P, 0, sizeof(T) * ldp * n0, s));
+        if (cross_mma) {
+            const int64_t kf = pairs_feature_cols<T>(K, d);
+            M->pvFq.ensure(sizeof(T) * ldp * kf);
+            M->featV.ensure(sizeof(T) * n0 * kf);
+            launch_pair_features<T>(K, Xall, n0, d, Xall, true, M->featV.as<T>(), n0, s);
+            launch_pair_features<T>(K, Xn, k, d, Xall, false, M->pvFq.as<T>(), ldp, s, M->flag.as<int>());
+            const KCanon<T>* kdev = M->kfit.put(K, s);
+            launch_kcross_mma<T>(K, kdev, M->pvFq.as<T>(), ldp, k, M->featV.as<T>(), n0, n0, d, P, ldp,
+                                 M->flag.as<int>(), s);
+        } else {
+            launch_kbuild<T>(K, Xn, tabNew, k, Xall, tabLead, n0, d, P, ldp, 0, false, T(0), M->flag.as<int>(), s);
+        }
+    }
+    // K(act, act) + s^2 I, identity-padded, straight into A[n0.., n0..)
+    T* S = A1 + n0 + n0 * ld1;
+    launch_kbuild<T>(K, Xact, tabAct, na, Xact, tabAct, na, d, S, ld1, nap, true, sigma2, M->flag.as<int>(), s);
+    GPRX_HIP(hipEventRecord(ctx->ev[1], s));
+    if (n0 > 0) {
+        if (gemm_new) trsm_rows<T>(A1, ld1, n0, Li1, P, ldp, ldp, s);
+        else launch_forward_panel_chain<T>(A1, ld1, n0, Li1, P, ldp, (int)k, M->info.as<int>(), ctx->ex, s);
+        launch_panel_rows<T>(P, ldp, k, n0, A1, ld1, n, s);
+        // S -= P P^T.  A small trailing block under a long panel (the one-sample update: one
+        // 128 x 128 tile, K = n0) is split over K, one 128-column slice per workgroup, and the
+        // partials are summed in order (as one product the C3 one-sample update spent 1.2 ms more
+        // of device time: 4.70 -> 3.52 ms, scripts/append_time.py)
+        const int64_t nb0 = n0 / DB;
+        if (nap <= 2 * DB && nb0 >= 8) {
+            M->apPart.ensure(sizeof(T) * nb0 * nap * nap);
+            GPRX_HIP(hipMemsetAsync(M->apPart.p, 0, sizeof(T) * nb0 * nap * nap, s));
+            launch_gemm_nt_splitk<T>(M->apPart.as<T>(), nap, nap * nap, A1 + n0, ld1, A1 + n0, ld1, nap, nap, DB,
+                                     (int)nb0, T(-1), true, s);
+            launch_schur_sum<T>(S, ld1, M->apPart.as<T>(), nap, (int)nb0, s);
+        } else {
+            launch_gemm_nt<T>(S, ld1, A1 + n0, ld1, A1 + n0, ld1, nap, nap, n0, T(-1), T(1), true, s);
+        }
+    }
+    potrf_auto<T>(S, ld1, nap, nap, Li1 + n0 * DB, M->info.as<int>(), ctx->ex);
+    GPRX_HIP(hipEventRecord(ctx->ev[2], s));
+    launch_label_rows<T>(M->Y.as<T>(), n1, m, A1, ld1, np1, np1, mp, s);
+    if (gemm) {
+        trsm_rows<T>(A1, ld1, np1, Li1, A1 + np1, ld1, mp, s);
+    } else {
+        for (int r0 = 0; r0 < m; r0 += DB)  // slabs of 128 label rows
+            launch_forward_panel_chain<T>(A1, ld1, np1, Li1, A1 + np1 + r0, ld1, std::min(DB, m - r0),
+                                          M->info.as<int>(), ctx->ex, s);
+    }
+    launch_fit_reductions<T>(A1, ld1, n1, np1, m, M->red.as<double>(), s);
+    launch_backsolve_chain<T>(A1, ld1, np1, m, Li1, M->apAlpha.as<T>(), M->info.as<int>(), ctx->ex, s);
+    GPRX_HIP(hipEventRecord(ctx->ev[3], s));
+    M->hstat.ensure(4 * sizeof(double));
+    volatile double* hs = static_cast<double*>(M->hstat.p);
+    launch_fit_status_gather(M->flag.as<int>(), M->info.as<int>(), M->red.as<double>(), M->hstat.dev, s);
+    GPRX_HIP(hipStreamSynchronize(s));
+    GPRX_HIP(hipGetLastError());
+    const double hred[2] = {hs[2], hs[3]};
+    const int hflag = reinterpret_cast<volatile int*>(hs)[0];
+    const int hinfo = reinterpret_cast<volatile int*>(hs + 1)[0];
+    if (hflag || hinfo < 0) {
+        restore();
+        if (hflag)
+            throw Error{GPRX_ERR_NONFINITE, "GaussianProcess::ComputeKernelMatrixInternal: kernel matrix contains "
+                                            "entries which are not finite."};
+        check_sched(hinfo);
+    }
+    if (hinfo != INT_MAX) return refit(fit_flags);  // not positive definite: the fit's LU fallback or NOT_SPD
+    // publish
+    if (relay) {
+        swap_buf(M->A, newA);
+        swap_buf(M->Linv, newLinv);
+    }
+    swap_buf(M->alpha, M->apAlpha);
+    M->n = n1;
+    M->np = np1;
+    M->ld = ld1;
+    M->inv_ready = false;
+    M->method = 0;
+    M->fitted = true;
+    M->has_alpha = true;
+    if (K.nper > 0) {
+        M->tab.ensure(sizeof(T) * 2 * K.nper * n1 * d);
+        launch_sincos_tables<T>(K, Xall, n1, d, M->tab.as<T>(), s);
+    }
+    if (out) {
+        std::memset(out, 0, sizeof(*out));
+        float t01 = 0, t12 = 0, t23 = 0;
+        hipEventElapsedTime(&t01, ctx->ev[0], ctx->ev[1]);
+        hipEventElapsedTime(&t12, ctx->ev[1], ctx->ev[2]);
+        hipEventElapsedTime(&t23, ctx->ev[2], ctx->ev[3]);
+        out->ms_build = t01;
+        out->ms_factor = t12;
+        out->ms_solve = t23;
+        out->logdet = hred[0];
+        out->datafit = hred[1];
+        out->appended = (int32_t)k;
+    }
+    if constexpr (std::is_same<T, float>::value) {
+        if (!(flags & GPRX_FIT_F32_NO_REFINE)) refine_f32(M, out);
+    }
+    return GPRX_OK;
 }
 
 // operator()(x, y) / GetCredibleInterval (lib/GaussianProcess.cpp:84-114) on a SHARDED fit:
@@ -2402,6 +2646,28 @@ gprx_status gprx_model_fit(gprx_model* M, uint32_t flags, gprx_fit_info* info) {
     API_END(ctx)
 }
 
+gprx_status gprx_model_append(gprx_model* M, const void* Xnew, const void* Ynew, int64_t k, uint32_t flags,
+                              gprx_fit_info* info) {
+    gprx_ctx* ctx = M ? M->ctx : nullptr;
+    API_BEGIN
+    GPRX_REQUIRE(M, GPRX_ERR_ARG, "gprx_model_append: NULL model");
+    GPRX_REQUIRE(!((ctx->hc && ctx->world > 1) || ctx->virt), GPRX_ERR_STATE,
+                 "gprx_model_append: sharded contexts (multi-rank or virtual-rank) refit in full: use gprx_model_set_data "
+                 "and gprx_model_fit");
+    GPRX_REQUIRE(Xnew && Ynew, GPRX_ERR_ARG, "gprx_model_append: NULL argument");
+    GPRX_REQUIRE(k > 0, GPRX_ERR_ARG, "gprx_model_append: the number of new samples must be positive");
+    ModelLock lk(M);
+    ProfBind pb_(ctx);  // after the lock: resolved (streams drained) before it is released
+    GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE,
+                 "gprx_model_append: a caller-evaluated kernel has no device form to extend the factor with");
+    GPRX_REQUIRE(!M->sparse_cov, GPRX_ERR_STATE, "gprx_model_append: a sparse-covariance model holds no factor");
+    GPRX_REQUIRE(M->fitted && M->has_data && M->has_kernel, GPRX_ERR_STATE,
+                 "GaussianProcess::AddSample: gaussian process is not initialized.");
+    return M->dt == GPRX_F64 ? model_append<double>(M, Xnew, Ynew, k, flags, info)
+                             : model_append<float>(M, Xnew, Ynew, k, flags, info);
+    API_END(ctx)
+}
+
 gprx_status gprx_model_get_alpha(gprx_model* M, void* alpha) {
     gprx_ctx* ctx = M ? M->ctx : nullptr;
     API_BEGIN
@@ -2744,6 +3010,17 @@ gprx_status gprx_dev_bench(gprx_ctx* ctx, gprx_dtype dtype, int32_t what, int64_
     gprx_status st = gprx_dev_bench_impl(dtype, what, M, N, K, iters, ms, &ctx->ex);
     if (st != GPRX_OK) return fail(ctx, st, "gprx_dev_bench failed");
     return GPRX_OK;
+    API_END(ctx)
+}
+
+gprx_status gprx_dev_forward_panel(gprx_ctx* ctx, gprx_dtype dtype, const void* L, int64_t n, void* R, int32_t rows,
+                                   int32_t use_gemm) {
+    API_BEGIN
+    GPRX_REQUIRE(ctx, GPRX_ERR_ARG, "gprx_dev_forward_panel: NULL context");
+    GPRX_REQUIRE(dtype == GPRX_F32 || dtype == GPRX_F64, GPRX_ERR_ARG, "gprx_dev_forward_panel: bad dtype");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPRX_HIP(hipSetDevice(ctx->device));
+    return gprx_dev_forward_panel_impl(dtype, L, n, R, rows, use_gemm, &ctx->ex, ctx->stream);
     API_END(ctx)
 }
 

@@ -1,6 +1,7 @@
 // gprx_dev.cpp — developer timing hooks (include/gprx_dev.h).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstring>
 #include <string>
@@ -205,6 +206,108 @@ static gprx_status bench_impl(int what, int64_t M, int64_t N, int64_t K, int ite
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return GPRX_OK;
+}
+
+// gprx_dev_forward_panel: the chained thin-panel solve (k_append.hip) or trsm_rows on a host
+// factor.  The diagonal blocks' inverses are formed on the host in double (forward substitution
+// of the identity).  The chained path's panel sits inside guard rows and columns of a fixed bit
+// pattern, compared bitwise afterwards: the kernel must touch rows < `rows` of its columns only.
+namespace gprx {
+template <typename T>
+void trsm_rows(const T* A, int64_t ldA, int64_t np, const T* Linv, T* R, int64_t ld, int64_t qp, hipStream_t s);
+
+template <typename T>
+static gprx_status forward_panel_impl(const void* Lh, int64_t n, void* Rh, int rows, int use_gemm, Exec& ex,
+                                      hipStream_t s) {
+    GPRX_REQUIRE(Lh && Rh && n > 0 && n % DB == 0 && rows >= 1 && rows <= DB, GPRX_ERR_ARG,
+                 "gprx_dev_forward_panel: n must be a positive multiple of 128 and 1 <= rows <= 128");
+    const T* L = static_cast<const T*>(Lh);
+    T* R = static_cast<T*>(Rh);
+    const int64_t nb = n / DB;
+    std::vector<T> hA((size_t)n * n, T(0)), hLi((size_t)n * DB, T(0));
+    for (int64_t i = 0; i < n; i++)
+        for (int64_t j = 0; j <= i; j++) hA[(size_t)i + (size_t)j * n] = L[(size_t)i * n + j];
+    std::vector<double> inv((size_t)DB * DB);
+    for (int64_t b = 0; b < nb; b++) {
+        const int64_t o = b * DB;
+        std::fill(inv.begin(), inv.end(), 0.0);
+        for (int c = 0; c < DB; c++)  // column c of the inverse: L x = e_c
+            for (int r = c; r < DB; r++) {
+                double v = (r == c) ? 1.0 : 0.0;
+                for (int q = c; q < r; q++) v -= (double)L[(size_t)(o + r) * n + o + q] * inv[(size_t)q + (size_t)c * DB];
+                inv[(size_t)r + (size_t)c * DB] = v / (double)L[(size_t)(o + r) * n + o + r];
+            }
+        for (size_t e = 0; e < (size_t)DB * DB; e++) hLi[(size_t)b * DB * DB + e] = (T)inv[e];
+    }
+    // the panel: guard rows below it and DB guard columns on either side
+    const int64_t gr = use_gemm ? 0 : 16, gc = use_gemm ? 0 : DB;
+    const int64_t ldr = (use_gemm ? (int64_t)DB : (int64_t)((rows + 15) / 16 * 16)) + gr, ncb = n + 2 * gc;
+    T guard;
+    std::memset(&guard, 0x5a, sizeof(T));
+    std::vector<T> hR((size_t)ldr * ncb, use_gemm ? T(0) : guard);
+    for (int64_t r = 0; r < rows; r++)
+        for (int64_t c = 0; c < n; c++) hR[(size_t)r + (size_t)(c + gc) * ldr] = R[(size_t)r * n + c];
+    std::vector<T> before = hR;
+    T *dA = nullptr, *dLi = nullptr, *dR = nullptr;
+    int* dinfo = nullptr;
+    gprx_status st = GPRX_OK;
+    std::string msg;
+    try {
+        GPRX_HIP(hipMalloc(&dA, sizeof(T) * hA.size()));
+        GPRX_HIP(hipMalloc(&dLi, sizeof(T) * hLi.size()));
+        GPRX_HIP(hipMalloc(&dR, sizeof(T) * hR.size()));
+        GPRX_HIP(hipMalloc(&dinfo, sizeof(int)));
+        GPRX_HIP(hipStreamSynchronize(s));
+        GPRX_HIP(hipMemcpy(dA, hA.data(), sizeof(T) * hA.size(), hipMemcpyHostToDevice));
+        GPRX_HIP(hipMemcpy(dLi, hLi.data(), sizeof(T) * hLi.size(), hipMemcpyHostToDevice));
+        GPRX_HIP(hipMemcpy(dR, hR.data(), sizeof(T) * hR.size(), hipMemcpyHostToDevice));
+        const int big = INT_MAX;
+        GPRX_HIP(hipMemcpy(dinfo, &big, sizeof(int), hipMemcpyHostToDevice));
+        if (use_gemm) trsm_rows<T>(dA, n, n, dLi, dR, ldr, ldr, s);
+        else launch_forward_panel_chain<T>(dA, n, n, dLi, dR + gc * ldr, ldr, rows, dinfo, ex, s);
+        GPRX_HIP(hipStreamSynchronize(s));
+        GPRX_HIP(hipGetLastError());
+        int hinfo = 0;
+        GPRX_HIP(hipMemcpy(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost));
+        GPRX_HIP(hipMemcpy(hR.data(), dR, sizeof(T) * hR.size(), hipMemcpyDeviceToHost));
+        GPRX_REQUIRE(hinfo >= 0, GPRX_ERR_HIP, "gprx_dev_forward_panel: a chained wait timed out");
+        if (!use_gemm)
+            for (int64_t c = 0; c < ncb; c++)
+                for (int64_t r = 0; r < ldr; r++) {
+                    if (r < rows && c >= gc && c < gc + n) continue;
+                    const size_t e = (size_t)r + (size_t)c * ldr;
+                    GPRX_REQUIRE(std::memcmp(&hR[e], &before[e], sizeof(T)) == 0, GPRX_ERR_HIP,
+                                 "gprx_dev_forward_panel: the kernel wrote outside its panel (row " +
+                                     std::to_string(r) + ", column " + std::to_string(c - gc) + ")");
+                }
+        for (int64_t r = 0; r < rows; r++)
+            for (int64_t c = 0; c < n; c++) R[(size_t)r * n + c] = hR[(size_t)r + (size_t)(c + gc) * ldr];
+    } catch (const Error& e) {
+        st = e.st;
+        msg = e.msg;
+    }
+    (void)hipFree(dA);
+    (void)hipFree(dLi);
+    (void)hipFree(dR);
+    (void)hipFree(dinfo);
+    if (st != GPRX_OK) throw Error{st, msg};
+    return GPRX_OK;
+}
+
+gprx_status gprx_dev_forward_panel_impl(gprx_dtype dtype, const void* L, int64_t n, void* R, int32_t rows,
+                                        int32_t use_gemm, Exec* ex, hipStream_t s) {
+    return dtype == GPRX_F64 ? forward_panel_impl<double>(L, n, R, rows, use_gemm, *ex, s)
+                             : forward_panel_impl<float>(L, n, R, rows, use_gemm, *ex, s);
+}
+}  // namespace gprx
+
+extern "C" int64_t gprx_dev_panel_trace(int64_t* times, int64_t max_blocks) {
+    try {
+        return gprx::ap_trace_copy((long long*)times, max_blocks);
+    } catch (const Error& e) {
+        std::fprintf(stderr, "gprx_dev_panel_trace: %s\n", e.msg.c_str());
+        return -1;
+    }
 }
 
 namespace gprx {

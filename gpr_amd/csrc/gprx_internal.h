@@ -627,6 +627,18 @@ void launch_backsolve_chain(const T* A, int64_t ld, int64_t np, int m, const T* 
 template <typename T>
 void launch_forward_chain(T* A, int64_t ld, int64_t np, int m, const T* Linv, int* info, Exec& ex, hipStream_t s);
 
+// Thin-panel forward substitution V L^T = R in place, one chained launch (k_append.hip): R is
+// rows (<= 128) x ncols, column-major (ldr), ncols a multiple of 128; only rows < `rows` are read
+// or written.  A timed-out wait sets *info = -1.
+template <typename T>
+void launch_forward_panel_chain(const T* A, int64_t ldA, int64_t ncols, const T* Linv, T* R, int64_t ldr, int rows,
+                                int* info, Exec& ex, hipStream_t s);
+// rows [0, rows) of the panel P (ldp) into rows r0 .. r0 + rows - 1 of A (ld), columns [0, ncols)
+template <typename T>
+void launch_panel_rows(const T* P, int64_t ldp, int64_t rows, int64_t ncols, T* A, int64_t ld, int64_t r0,
+                       hipStream_t s);
+int64_t ap_trace_copy(long long* out, int64_t max_blocks);
+
 // logdet partial = 2 sum log L_ii over i < n, datafit = sum of squares of the augmented
 // rows; results accumulated in double on the device (out[0], out[1]).
 template <typename T>

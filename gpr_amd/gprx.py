@@ -25,6 +25,7 @@ FIT_NO_LU_FALLBACK = 1
 FIT_DISTRIBUTED = 2
 FIT_FORCE_LU = 8
 FIT_F32_NO_REFINE = 4
+APPEND_SOLVE_GEMM = 16  # Model.append: panel solves through trsm_rows, not the chained panel kernel
 LML_GRAD = 1
 LML_COMPAT = 2
 LML_DISTRIBUTED = 4
@@ -46,6 +47,7 @@ EXPORTED = [
     "gprx_model_set_kernel_matrix", "gprx_model_predict_kx", "gprx_model_posterior_cov_kx", "gprx_model_lml_dk",
     "gprx_model_set_sparse_cov", "gprx_sparse_lml",
     "gprx_device_alloc", "gprx_device_free", "gprx_device_upload", "gprx_device_download",
+    "gprx_model_append",
 ]
 
 
@@ -73,7 +75,7 @@ class FitInfo(ctypes.Structure):
     _fields_ = [("logdet", ctypes.c_double), ("datafit", ctypes.c_double), ("info", ctypes.c_int32),
                 ("method", ctypes.c_int32), ("ms_build", ctypes.c_double), ("ms_factor", ctypes.c_double),
                 ("ms_solve", ctypes.c_double), ("ms_refine", ctypes.c_double), ("refine_delta", ctypes.c_double),
-                ("refine_steps", ctypes.c_int32), ("pad", ctypes.c_int32)]
+                ("refine_steps", ctypes.c_int32), ("appended", ctypes.c_int32)]
 
 
 _lib = None
@@ -131,6 +133,8 @@ def lib():
         L.gprx_model_set_kernel.argtypes = [ctypes.c_void_p, ctypes.POINTER(KernelDesc)]
         L.gprx_model_set_noise.argtypes = [ctypes.c_void_p, ctypes.c_double]
         L.gprx_model_fit.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(FitInfo)]
+        L.gprx_model_append.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
+                                        ctypes.c_uint32, ctypes.POINTER(FitInfo)]
         L.gprx_model_get_alpha.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_set_alpha.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_predict.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -180,6 +184,10 @@ def lib():
         L.gprx_dev_build_time.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(KernelDesc),
                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_double,
                                           ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
+        L.gprx_dev_forward_panel.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
+        L.gprx_dev_panel_trace.restype = ctypes.c_int64
+        L.gprx_dev_panel_trace.argtypes = [ctypes.c_void_p, ctypes.c_int64]
         _lib = L
     return _lib
 
@@ -466,6 +474,25 @@ class Context:
                                           float(sigma), path, iters, ctypes.byref(ms)))
         return ms.value
 
+    def forward_panel(self, L, R, use_gemm=False):
+        """V with V L^T = R for a lower factor L (n x n, n a multiple of 128) and a panel R of at
+        most 128 rows (rows x n): the chained thin-panel kernel of Model.append alone
+        (gprx_dev_forward_panel), or the same solve through trsm_rows (use_gemm)."""
+        L = np.ascontiguousarray(L)
+        V = np.array(R, dtype=L.dtype, copy=True, order="C")
+        if V.ndim != 2 or L.ndim != 2 or L.shape[0] != L.shape[1] or V.shape[1] != L.shape[0]:
+            raise ValueError("forward_panel: L is n x n, R is rows x n")
+        self._c(lib().gprx_dev_forward_panel(self.h, _dt(L.dtype), _ptr(L), L.shape[0], _ptr(V), V.shape[0],
+                                             1 if use_gemm else 0))
+        return V
+
+    def panel_trace(self, max_blocks=4096):
+        """GPRX_BS_TRACE=1: per 128-column block of the last chained panel launch {start, streamed
+        tiles done, the same, published} in 100 MHz ticks (gprx_dev_panel_trace)."""
+        t = np.zeros((max_blocks, 4), np.int64)
+        nb = lib().gprx_dev_panel_trace(_ptr(t), max_blocks)
+        return t[:max(nb, 0)].copy()
+
     def cholesky(self, A):
         A = np.array(A, copy=True, order="C")
         info = ctypes.c_int32()
@@ -603,6 +630,42 @@ class Model:
     def fit(self, flags=FIT_DEFAULT):
         info = FitInfo()
         self._c(lib().gprx_model_fit(self.h, flags, ctypes.byref(info)))
+        return info
+
+    def append(self, Xnew, Ynew, flags=0):
+        """Add the samples Xnew (k x d), Ynew (k x m) to a fitted model by extending its Cholesky
+        factor (gprx_model_append): O(N^2 k) instead of the refit's O(N^3).  Host arrays, or
+        DeviceArrays of this context, as set_data.  flags: FIT_NO_LU_FALLBACK, FIT_F32_NO_REFINE,
+        APPEND_SOLVE_GEMM.  info.appended = k, or 0 when the call had to refit in full."""
+        dev = isinstance(Xnew, DeviceArray) or isinstance(Ynew, DeviceArray)
+        if dev:
+            if not (isinstance(Xnew, DeviceArray) and isinstance(Ynew, DeviceArray)) or Xnew.dtype != self.dtype \
+                    or Ynew.dtype != self.dtype:
+                raise TypeError("append: Xnew and Ynew both DeviceArrays of the model's dtype, or both host arrays")
+            xs = tuple(Xnew.shape)
+            ys = tuple(Ynew.shape) if len(Ynew.shape) > 1 else (Ynew.shape[0], 1)
+        else:
+            Xnew = np.ascontiguousarray(Xnew, self.dtype)
+            Ynew = np.ascontiguousarray(Ynew, self.dtype)
+            if Xnew.ndim == 1:
+                Xnew = Xnew[None, :]
+            if Ynew.ndim == 1:
+                Ynew = Ynew[:, None]
+            xs, ys = Xnew.shape, Ynew.shape
+        if self.n and (len(xs) != 2 or xs[1] != self.d or ys[1] != self.m or ys[0] != xs[0]):
+            raise GprxError(4, f"append: new samples of shape {tuple(xs)} / {tuple(ys)}, the model holds "
+                               f"d = {self.d}, m = {self.m}")
+        k = xs[0]
+        info = FitInfo()
+        try:
+            self._c(lib().gprx_model_append(self.h, _ptr(Xnew), _ptr(Ynew), k, flags, ctypes.byref(info)))
+        except GprxError as e:
+            if e.status in (2, 3):  # the full refit of the extended data failed: the model holds them, unfitted
+                self.n += k
+                self._Xh = None if (dev or self._Xh is None) else np.concatenate([self._Xh, Xnew])
+            raise
+        self.n += k
+        self._Xh = None if (dev or self._Xh is None) else np.concatenate([self._Xh, Xnew])
         return info
 
     def dist_info(self):

@@ -89,15 +89,14 @@ void GaussianProcess<T>::AddSample(const VectorType& x, const VectorType& y) {
     CheckOutputDimension(y, "GaussianProcess::AddSample: ");
     m_SampleVectors.push_back(x);
     m_LabelVectors.push_back(y);
-    m_Initialized = false;
-    m_DataUploaded = false;
+    m_Initialized = false;  // (the device keeps its prefix of the samples: m_DeviceSamples)
 }
 
 template <class T>
 void GaussianProcess<T>::UploadState() {
     gprx_ctx* ctx = DefaultContext();
     const std::size_t n = m_SampleVectors.size();
-    if (!m_DataUploaded || !m_Model) {
+    if (!m_DataUploaded || !m_Model || m_DeviceSamples != n) {
         const std::size_t d = m_InputDimension, m = m_OutputDimension;
         std::vector<T> X(n * d), Y(n * m);
         for (std::size_t i = 0; i < n; i++) {
@@ -106,6 +105,7 @@ void GaussianProcess<T>::UploadState() {
         }
         ThrowIfFailed(gprx_model_set_data(Model(), X.data(), Y.data(), (int64_t)n, (int32_t)d, (int32_t)m), ctx);
         m_DataUploaded = true;
+        m_DeviceSamples = n;
     }
     std::vector<gprx_knode> prog;
     try {
@@ -156,6 +156,9 @@ void GaussianProcess<T>::FitDevice(gprx_fit_info* info) {
     ThrowIfFailed(gprx_model_fit(m_Model, flags, &fi), DefaultContext());
     if (info) *info = fi;
     m_DeviceFactor = true;
+    m_FitCholesky = fi.method == 0 && !m_HostKernel;
+    m_FitKernel = m_FitCholesky ? m_Kernel->ToString() : std::string();
+    m_FitSigma = m_Sigma;
 }
 
 // The factor for operator()/core matrix.  A GP whose regression vectors are fixed (loaded
@@ -213,6 +216,42 @@ void GaussianProcess<T>::Initialize() {
     // lib/GaussianProcess.cpp:652-668: the core exists unless efficient storage drops it
     m_CoreSize = m_EfficientStorage ? 0 : m_SampleVectors.size();
     m_Initialized = true;
+}
+
+template <class T>
+void GaussianProcess<T>::Update() {
+    const std::size_t n = m_SampleVectors.size();
+    bool extended = false;
+    if (!m_Initialized && n > 0 && m_LabelVectors.size() == n) {
+        std::lock_guard<std::mutex> lk(m_DevMu);
+        const bool svd = m_InvMethod == JacobiSVD || m_InvMethod == BDCSVD;
+        if (m_Model && m_DeviceFactor && m_FitCholesky && !svd && m_DataUploaded && m_DeviceSamples > 0 &&
+            m_DeviceSamples < n && m_FitSigma == m_Sigma && m_FitKernel == m_Kernel->ToString()) {
+            const std::size_t d = m_InputDimension, m = m_OutputDimension, n0 = m_DeviceSamples, c = n - n0;
+            std::vector<T> X(c * d), Y(c * m);
+            for (std::size_t i = 0; i < c; i++) {
+                for (std::size_t k = 0; k < d; k++) X[i * d + k] = m_SampleVectors[n0 + i][k];
+                for (std::size_t q = 0; q < m; q++) Y[i * m + q] = m_LabelVectors[n0 + i][q];
+            }
+            gprx_fit_info fi;
+            const gprx_status st = gprx_model_append(m_Model, X.data(), Y.data(), (int64_t)c, GPRX_FIT_DEFAULT, &fi);
+            if (st != GPRX_OK) {  // whatever the device holds now, the next fit re-sends everything
+                m_DataUploaded = false;
+                m_DeviceFactor = false;
+                ThrowIfFailed(st, DefaultContext());
+            }
+            m_DeviceSamples = n;
+            m_FitCholesky = fi.method == 0;
+            m_RegressionVectors.resize(n, m_OutputDimension);
+            ThrowIfFailed(gprx_model_get_alpha(m_Model, m_RegressionVectors.data()), DefaultContext());
+            m_CoreValid = false;
+            m_CoreMatrix.resize(0, 0);
+            m_CoreSize = m_EfficientStorage ? 0 : n;
+            m_Initialized = true;
+            extended = true;
+        }
+    }
+    if (!extended) Initialize();
 }
 
 template <class T>

@@ -77,6 +77,12 @@ public:
     virtual TScalarType operator()(const VectorType& x, const VectorType& y);
     TScalarType GetCredibleInterval(const VectorType& x);
     virtual void Initialize();
+    // Initialize() for a GP that only GREW since its last device fit: when the device holds a
+    // Cholesky factor made with the current kernel and sigma and the only change since is c >= 1
+    // AddSample calls, the c new samples extend that factor (gprx_model_append, O(N^2 c)) instead
+    // of the O(N^3) refit; in every other state this is Initialize().  Opt-in: Initialize() and
+    // the calls that imply it always refit.  Not in the reference.
+    virtual void Update();
 
     // Batched, device-native forms (one launch for all rows; not in the reference).
     MatrixType PredictBatch(const MatrixType& Xq);                 // rows = queries -> q x m
@@ -136,9 +142,17 @@ protected:
                                   // kernel vectors are evaluated here through the virtual
                                   // operator() (include/Kernel.h:52-59), the rest on the device
     bool m_CoreValid = false;     // m_CoreMatrix holds the materialised core matrix
-    bool m_DataUploaded = false;  // the device model holds the current samples (AddSample clears
-                                  // it): an optimiser loop re-evaluating the likelihood under new
-                                  // kernel parameters re-sends only the kernel
+    bool m_DataUploaded = false;  // the device model holds the first m_DeviceSamples samples as
+                                  // they are here: an optimiser loop re-evaluating the likelihood
+                                  // under new kernel parameters re-sends only the kernel, and
+                                  // Update() only the samples added since
+    std::size_t m_DeviceSamples = 0;  // samples resident on the device (UploadState re-sends all
+                                      // of them when it differs from the sample count)
+    // the device factor's provenance (FitDevice, Update): a Cholesky factor, and the kernel and
+    // sigma it was made with -- Update() extends it only while these still hold
+    bool m_FitCholesky = false;
+    std::string m_FitKernel;
+    TScalarType m_FitSigma = 0;
     std::size_t m_CoreSize = 0;   // the reference's m_CoreMatrix.diagonalSize(): n once the
                                   // core exists (Initialize w/o efficient storage, operator(),
                                   // Load), 0 when efficient storage dropped it

@@ -79,6 +79,7 @@ protected:
                           DefaultContext());
         }
         gp->m_DeviceFactor = true;
+        gp->m_FitCholesky = false;  // (not a factor Update() may extend: it refits)
         gp->m_CoreValid = false;
         // the likelihood does not change the gp's regression vectors (the reference only
         // reads its core matrix): keep predicting with them

@@ -104,7 +104,7 @@ typedef struct gprx_fit_info {
     double ms_refine;    /* fp32 models: device time of the fp64 iterative refinement */
     double refine_delta; /* fp32 models: |last correction|_inf / |alpha|_inf (0 if not refined) */
     int32_t refine_steps;/* fp32 models: refinement steps taken */
-    int32_t pad;
+    int32_t appended;    /* gprx_model_append: rows added by extending the factor (0: a full refit) */
 } gprx_fit_info;
 
 /* ---- library / context ---------------------------------------------------------- */
@@ -219,6 +219,24 @@ gprx_status gprx_model_set_noise(gprx_model* model, double sigma);
  * vectors alpha = (K + sigma^2 I)^{-1} Y (:661).  Everything stays in HBM; `info` may be
  * NULL. */
 gprx_status gprx_model_fit(gprx_model* model, uint32_t flags, gprx_fit_info* info);
+/* AddSample x k (lib/GaussianProcess.cpp:36-51) + Initialize on a FITTED model without the O(N^3)
+ * refit: the Cholesky factor is extended by the k new rows (Xnew k x d, Ynew k x m, row-major in
+ * the model's dtype, host or device memory).  Rows below the last full 128-block boundary of the
+ * factor are kept; the old partial block and the new samples are refactored against them
+ * (O(N^2 k) for the new rows' panel K(Xnew, X) L00^{-T} and the Schur complement), then the
+ * labels' forward solve and alpha are redone against the whole factor (O(N^2 m)).  predict,
+ * posterior_cov, core_matrix and lml then see all n + k samples.
+ * flags: GPRX_FIT_NO_LU_FALLBACK, GPRX_FIT_F32_NO_REFINE as for a fit, GPRX_APPEND_SOLVE_GEMM.
+ * info->appended = k.  A model whose factor is the LU, or an update whose trailing Cholesky meets
+ * a non-positive pivot, extends the data and refits in full (info->appended = 0, then the fit's
+ * LU fallback or GPRX_ERR_NOT_SPD).  GPRX_ERR_STATE, model untouched: not fitted, a
+ * caller-evaluated kernel, a sparse-covariance model, a sharded (multi-rank or virtual-rank)
+ * context.  GPRX_ERR_NONFINITE (a non-finite new kernel entry) leaves the fitted model as it
+ * was. */
+#define GPRX_APPEND_SOLVE_GEMM 16u /* panel solves through the GEMM triangular solve (trsm_rows)
+                                      instead of the chained panel kernel (k_append.hip) */
+gprx_status gprx_model_append(gprx_model* model, const void* Xnew, const void* Ynew, int64_t k, uint32_t flags,
+                              gprx_fit_info* info);
 /* m_RegressionVectors (lib/GaussianProcess.cpp:661) -> host, N x m. */
 gprx_status gprx_model_get_alpha(gprx_model* model, void* alpha);
 /* Install regression vectors (n x m, row-major) read back by GaussianProcess::Load

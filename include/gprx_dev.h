@@ -104,6 +104,15 @@ gprx_status gprx_dev_diag_factor(gprx_ctx* ctx, int32_t variant, const double* A
 /* The pair-statistics epilogues' f64 exp (gprx_internal.h fexp) on n host values (accuracy
  * test against the C library). */
 gprx_status gprx_dev_fexp(gprx_ctx* ctx, const double* x, int64_t n, double* y);
+/* Parity hook for the chained thin-panel forward substitution (k_append.hip): V L^T = R for the
+ * host row-major lower factor L (n x n, n a multiple of 128) and the host row-major panel R
+ * (rows x n, rows <= 128), solved in place.  use_gemm != 0: the same solve through trsm_rows
+ * (the panel padded to 128 rows), the path it is compared with.
+ * GPRX_BS_TRACE=1: gprx_dev_panel_trace returns per block of the last panel launch {start,
+ * streamed tiles done, the same, V_b published} (100 MHz wall clock); returns blocks. */
+gprx_status gprx_dev_forward_panel(gprx_ctx* ctx, gprx_dtype dtype, const void* L, int64_t n, void* R, int32_t rows,
+                                   int32_t use_gemm);
+int64_t gprx_dev_panel_trace(int64_t* times, int64_t max_blocks);
 #ifdef __cplusplus
 }
 #endif
