@@ -832,7 +832,7 @@ static DSArgs<T> make_dsargs(const DistEngine<T>& E, const DistRank<T>& R) {
     a.sep = E.sep;
     a.ctl = R.sctl.template as<int>();
     a.info = R.info.template as<int>();
-    a.tlimit = (long long)(1e8 * 4.0);
+    a.tlimit = CHAIN_TLIMIT_TICKS;
     return a;
 }
 
@@ -1292,7 +1292,7 @@ void dist_posterior(DistEngineBase* eng, const KCanon<T>& K, const T* X, const T
         a.part = Rk.pvpart.template as<double>();
         a.ctl = Rk.sctl.template as<int>();
         a.info = Rk.info.template as<int>();
-        a.tlimit = (long long)(1e8 * 4.0);
+        a.tlimit = CHAIN_TLIMIT_TICKS;
         if (a.nown > 0) launch_dist_pvar<T>(a, E.P, Rk.s);
     }
     int hinfo = INT_MAX;

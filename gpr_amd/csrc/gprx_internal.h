@@ -616,6 +616,34 @@ bool launch_gemm_tall(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
 template <typename T>
 void launch_backsolve(const T* A, int64_t ld, int64_t np, int m, const T* Linv, T* z, T* alpha, hipStream_t s);
 
+// Time limit of one wait of a chained launch (k_handoff.h, wait_until): 4 s of the 100 MHz wall
+// clock.  (The factorisation's limits depend on its schedule: k_ptiles.hip, gprx_dist.cpp.)
+constexpr long long CHAIN_TLIMIT_TICKS = 400000000LL;
+
+// GPRX_BS_TRACE timeline of the last launch of a chain kernel: four wall-clock stamps (100 MHz)
+// per block, in device memory.
+struct BlockTrace {
+    long long* dev = nullptr;
+    int n = 0;
+    // the buffer for a launch of nb blocks (grown when needed)
+    long long* ensure(int nb) {
+        if (n < nb) {
+            if (dev) GPRX_HIP(hipFree(dev));
+            GPRX_HIP(hipMalloc(&dev, sizeof(long long) * 4 * nb));
+        }
+        n = nb;
+        return dev;
+    }
+    // the stamps of the first min(max_blocks, n) blocks to the host; returns that count
+    int64_t copy(long long* out, int64_t max_blocks) const {
+        if (!dev) return 0;
+        const int64_t nc = max_blocks < n ? max_blocks : n;
+        GPRX_HIP(hipDeviceSynchronize());
+        GPRX_HIP(hipMemcpy(out, dev, sizeof(long long) * 4 * nc, hipMemcpyDeviceToHost));
+        return nc;
+    }
+};
+
 // Same solve in one launch: one workgroup per 128-block, chained by flags (k_bsolve.hip).
 // z is read from the label rows np..np+m-1 of A (ld).  A timed-out wait sets *info = -1.
 // tiles/tld (optional, the distributed factor): tile (j, k) at tiles[j * (np/128) + k] with

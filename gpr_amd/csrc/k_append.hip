@@ -12,16 +12,13 @@
 // 16-row groups: per streamed tile L_bj a lane keeps its 32 operand values (row 16 w + lr,
 // k-columns 4 q + lk) in registers and V_j comes through LDS.
 //
-// Chaining as in k_bsolve.hip: blocks are claimed through a ticket counter (first block
-// first), so a workgroup waits only on blocks claimed by workgroups already running; the
-// loads of tile L_bj go out before V_j is waited for (and tile j + 1's before tile j is
-// multiplied).  V_b is handed off with sc1 (write-through) stores, a drain of every storing
-// wave, a workgroup barrier and one relaxed agent-scope flag per block from one lane; every
-// consuming wave polls the flag itself and then reads V_j with sc1 loads only
-// (MI355X_MICROARCH.md, inter-workgroup visibility, "Valid forms", first row of the table; the
-// launch asks for more than half a CU's LDS, so one workgroup per CU).  Waits are bounded in
-// wall-clock time; a timeout sets the error word, drains every workgroup and *info = -1.
+// Blocks are claimed first block first and chained by the hand-off protocol of k_handoff.h
+// (tickets, sc1 stores and loads, one flag per block, bounded waits).  Specific to this file:
+// the loads of tile L_bj go out before V_j is waited for (and tile j + 1's before tile j is
+// multiplied); every consuming wave polls the flag itself; the launch asks for more than half a
+// CU's LDS, so one workgroup per CU (the table's first row requires it).
 #include "gprx_internal.h"
+#include "k_handoff.h"
 #include "k_mma.h"
 
 #include <algorithm>
@@ -31,8 +28,9 @@ namespace gprx {
 
 namespace ap {
 
+using namespace ho;
+
 constexpr int NT = 512;  // 8 waves
-enum { C_TICKET = 0, C_ERR = 1, C_NCTL = 4 };
 constexpr size_t LDS_MIN = 84 * 1024;  // more than half of the CU's 160 KB: one workgroup per CU
 
 // LDS leading dimension of a staged panel of RG 16-row groups: the four k-columns a fragment
@@ -44,34 +42,12 @@ constexpr size_t panel_lds() {
     return need > LDS_MIN ? need : LDS_MIN;
 }
 
-__device__ __forceinline__ int ld_uni(const int* p) {
-    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-template <typename T>
-__device__ __forceinline__ T ld_sc1(const T* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-__device__ __forceinline__ void st_sc1(T* p, T v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
 // Wait until *f != 0; false on timeout or another workgroup's error (every wave polls on its
 // own and the workgroup agrees through LDS at its next barrier).
 __device__ __forceinline__ bool wait_flag(const int* f, int* ctl, long long t0, long long tlimit) {
     // (the error word and the clock every 16th poll: each is a round trip of its own between two
     // looks at the flag)
-    for (int spins = 1; ld_uni(f) == 0; spins++) {
-        if ((spins & 15) == 0) {
-            if (ld_uni(ctl + C_ERR)) return false;
-            if (wall_clock64() - t0 > tlimit) {
-                __hip_atomic_store(ctl + C_ERR, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                return false;
-            }
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    return true;
+    return wait_until<1, 16>([=] { return ld_uni(f) != 0; }, ctl + C_ERR, t0, tlimit);
 }
 
 template <typename T>
@@ -121,14 +97,10 @@ __global__ __launch_bounds__(NT) void forward_panel_kernel(Args<T> a) {
     const int lr = lane & 15, lk = lane >> 4;
     int* flags = a.ctl + C_NCTL;
     if (w == 0) {
-        const int v = __hip_atomic_fetch_add(a.ctl + C_TICKET, (t == 0) ? 1 : 0, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-        s_int[0] = __builtin_amdgcn_readfirstlane(v);
         s_int[1] = 0;
         s_int[2] = 0;
     }
-    __syncthreads();
-    const int b = __builtin_amdgcn_readfirstlane(s_int[0]);
+    const int b = claim_ticket(a.ctl, &s_int[0]);
     if (b >= a.nb) return;
     if (a.trace && t == 0) a.trace[4 * b] = wall_clock64();
     const long long t0 = wall_clock64();
@@ -243,10 +215,12 @@ __global__ __launch_bounds__(NT) void forward_panel_kernel(Args<T> a) {
                 if (r < a.rows) st_sc1(Rb + r + (int64_t)c * a.ldr, acc[g][reg]);
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        // the publish of k_handoff.h with the flag stored from ONE lane (the guide's first row; no
+        // loop follows it here): publish_flag's wave-0 form cost the 8-group f64 panel, which sits
+        // at 256 VGPRs, a 12-byte spill
+        local_sync();
         if (t == 0) {
-            __hip_atomic_store(flags + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            st_agent(flags + b, 1);
             if (a.trace) a.trace[4 * b + 3] = wall_clock64();
         }
     }
@@ -277,16 +251,9 @@ __global__ void schur_sum_kernel(T* __restrict__ S, int64_t lds, const T* __rest
 
 }  // namespace ap
 
-// GPRX_BS_TRACE timeline of the last panel launch (per block, 100 MHz wall clock)
-static long long* g_ap_trace = nullptr;
-static int g_ap_trace_n = 0;
-int64_t ap_trace_copy(long long* out, int64_t max_blocks) {
-    if (!g_ap_trace) return 0;
-    const int64_t n = std::min<int64_t>(max_blocks, g_ap_trace_n);
-    GPRX_HIP(hipDeviceSynchronize());
-    GPRX_HIP(hipMemcpy(out, g_ap_trace, sizeof(long long) * 4 * n, hipMemcpyDeviceToHost));
-    return n;
-}
+// GPRX_BS_TRACE timeline of the last panel launch
+static BlockTrace g_ap_trace;
+int64_t ap_trace_copy(long long* out, int64_t max_blocks) { return g_ap_trace.copy(out, max_blocks); }
 
 template <typename T, int RG>
 static void launch_panel_rg(const ap::Args<T>& a, hipStream_t s) {
@@ -325,16 +292,9 @@ void launch_forward_panel_chain(const T* A, int64_t ldA, int64_t ncols, const T*
     a.rows = rows;
     a.ctl = scratch;
     a.info = info;
-    a.tlimit = (long long)(1e8 * 4.0);
+    a.tlimit = CHAIN_TLIMIT_TICKS;
     static const bool tracing = std::getenv("GPRX_BS_TRACE") != nullptr;
-    if (tracing) {
-        if (g_ap_trace_n < nb) {
-            if (g_ap_trace) GPRX_HIP(hipFree(g_ap_trace));
-            GPRX_HIP(hipMalloc(&g_ap_trace, sizeof(long long) * 4 * nb));
-        }
-        g_ap_trace_n = nb;
-        a.trace = g_ap_trace;
-    }
+    if (tracing) a.trace = g_ap_trace.ensure(nb);
     const int rg = (rows + 15) / 16;
     if (rg <= 1) launch_panel_rg<T, 1>(a, s);
     else if (rg <= 2) launch_panel_rg<T, 2>(a, s);

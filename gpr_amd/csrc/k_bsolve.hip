@@ -11,14 +11,12 @@
 // are published, and publishes alpha_k when done: the critical path per block is one
 // 128 x 128 tile GEMV, the diagonal-block solve and one hand-off.
 //
-// Blocks are claimed through a ticket counter (last block first), so every workgroup waits
-// only on blocks claimed by workgroups already running: no deadlock whatever the dispatch
-// order.  alpha is handed off with sc1 (write-through) stores and sc1 loads and a relaxed
-// agent-scope flag per block after every storing wave drained its stores
-// (MI355X_MICROARCH.md, inter-workgroup visibility, "Valid forms"); the factor itself was
-// written by the previous kernel.  Waits are bounded in wall-clock time; a timeout sets the
-// error word, drains every workgroup and is reported by the caller.
+// Blocks are claimed last block first and chained by the hand-off protocol of k_handoff.h
+// (tickets, sc1 stores and loads, one flag per block and right-hand side, bounded waits); the
+// factor itself was written by the previous kernel.  Specific to this file: the consumer of
+// alpha_j polls alpha's values themselves against a NaN sentinel (unset(), below).
 #include "gprx_internal.h"
+#include "k_handoff.h"
 
 #include <algorithm>
 #include <cstring>
@@ -27,27 +25,16 @@ namespace gprx {
 
 namespace bs {
 
+using namespace ho;
+
 constexpr int NT = 512;        // 8 waves
 constexpr int QR = DB / 4;     // rows per thread in the column layout: thread t -> column
                                // c = t & 127, rows QR q .. QR q + QR - 1, q = t >> 7
 constexpr int CPW = DB / 8;    // streamed tiles: wave w sums columns CPW w .. CPW w + CPW - 1
-enum { C_TICKET = 0, C_ERR = 1, C_NCTL = 4 };
 constexpr int LDL = DB + 1;    // padded LDS column of Linv_k (2-way bank conflicts at most)
 template <typename T>
 constexpr size_t bs_lds() {
     return sizeof(T) * (size_t)DB * LDL;
-}
-
-__device__ __forceinline__ int ld_uni(const int* p) {
-    return __builtin_amdgcn_readfirstlane(__hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-}
-template <typename T>
-__device__ __forceinline__ T ld_sc1(const T* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename T>
-__device__ __forceinline__ void st_sc1(T* p, T v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // A streamed tile's share of one lane: rows 2l, 2l+1 of the wave's CPW columns (one 16-byte
@@ -121,15 +108,7 @@ __device__ __forceinline__ const T* bs_tile(const Args<T>& a, int j, int k, int 
 // Wait until *f != 0; false on timeout or another workgroup's error (every wave polls on its
 // own: the caller agrees through LDS before the next barrier).
 __device__ __forceinline__ bool wait_flag(const int* f, int* ctl, long long t0, long long tlimit) {
-    while (ld_uni(f) == 0) {
-        if (ld_uni(ctl + C_ERR)) return false;
-        if (wall_clock64() - t0 > tlimit) {
-            __hip_atomic_store(ctl + C_ERR, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    return true;
+    return wait_until([=] { return ld_uni(f) != 0; }, ctl + C_ERR, t0, tlimit);
 }
 
 // alpha is pre-filled with a NaN of a fixed payload (bs_init_kernel): a consumer polls the
@@ -189,13 +168,7 @@ __global__ __launch_bounds__(NT) void backsolve_chain_kernel(Args<T> a) {
     const int c = t & (DB - 1), q = t >> 7;
     const int nb = (int)(a.np / DB);
     int* flags = a.ctl + C_NCTL;
-    if (w == 0) {
-        const int v = __hip_atomic_fetch_add(a.ctl + C_TICKET, (t == 0) ? 1 : 0, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-        s_int[0] = __builtin_amdgcn_readfirstlane(v);
-    }
-    __syncthreads();
-    const int tk = __builtin_amdgcn_readfirstlane(s_int[0]);
+    const int tk = claim_ticket(a.ctl, &s_int[0]);
     if (tk >= nb) return;
     const int k = nb - 1 - tk;
     const int64_t r0 = (int64_t)k * DB;
@@ -212,14 +185,6 @@ __global__ __launch_bounds__(NT) void backsolve_chain_kernel(Args<T> a) {
         const T* p1 = bs_tile<T>(a, k + 1, k, nb, l1);
         load_run<T>(p1 + (int64_t)c * l1 + QR * q, t1);
     }
-    // agree on a failed wait (waves poll on their own) before using the barriers' results
-    auto agree = [&](bool ok) {
-        if (t == 0) s_int[1] = 0;
-        __syncthreads();
-        if (!ok) s_int[1] = 1;  // (any lane: the alpha poll fails per lane)
-        __syncthreads();
-        return s_int[1] == 0;
-    };
     bool ok = true;
     for (int r = 0; r < a.m && ok; r++) {
         int* fl = flags + (int64_t)r * nb;
@@ -243,21 +208,14 @@ __global__ __launch_bounds__(NT) void backsolve_chain_kernel(Args<T> a) {
             const int64_t rj = (int64_t)j * DB + 2 * lane;
             const T* p0 = a.alpha + rj * a.m + r;
             const T* p1 = a.alpha + (rj + 1) * a.m + r;
-            T v0 = ld_sc1(p0), v1 = ld_sc1(p1);
-            while (unset(v0) || unset(v1)) {
-                if (__hip_atomic_load(a.ctl + C_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                    ok = false;
-                    break;
-                }
-                if (wall_clock64() - t0 > a.tlimit) {
-                    __hip_atomic_store(a.ctl + C_ERR, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    ok = false;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-                v0 = ld_sc1(p0);
-                v1 = ld_sc1(p1);
-            }
+            T v0, v1;
+            ok = wait_until(
+                [&] {
+                    v0 = ld_sc1(p0);
+                    v1 = ld_sc1(p1);
+                    return !(unset(v0) || unset(v1));
+                },
+                a.ctl + C_ERR, t0, a.tlimit);
             // (a lane that failed leaves the loop at once; the others find the error word set)
             if (!__builtin_amdgcn_readfirstlane(__ballot(ok) == __ballot(1))) {
                 ok = false;
@@ -265,7 +223,8 @@ __global__ __launch_bounds__(NT) void backsolve_chain_kernel(Args<T> a) {
             }
             tr.apply(v0, v1, p);
         }
-        if (!agree(ok)) break;
+        // agree on a failed wait (waves poll on their own) before using the barriers' results
+        if (!agree(ok, &s_int[1])) break;
         {
             int col;
             const T sum = wave_reduce_cols<T>(p, lane, col);
@@ -278,24 +237,17 @@ __global__ __launch_bounds__(NT) void backsolve_chain_kernel(Args<T> a) {
             // alpha_{k+1} polled value by value (lanes of waves 0-1), straight into s_alpha
             if (t < DB) {
                 const T* ap = a.alpha + ((int64_t)(k + 1) * DB + t) * a.m + r;
-                T v = ld_sc1(ap);
-                while (unset(v)) {
-                    if (__hip_atomic_load(a.ctl + C_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-                        ok = false;
-                        break;
-                    }
-                    if (wall_clock64() - t0 > a.tlimit) {
-                        __hip_atomic_store(a.ctl + C_ERR, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        ok = false;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                    v = ld_sc1(ap);
-                }
+                T v;
+                ok = wait_until(
+                    [&] {
+                        v = ld_sc1(ap);
+                        return !unset(v);
+                    },
+                    a.ctl + C_ERR, t0, a.tlimit);
                 s_alpha[t] = v;
             }
             if (a.trace && r == 0 && t == 0) a.trace[4 * k + 2] = wall_clock64();
-            if (!agree(ok)) break;  // (its barriers also publish s_alpha)
+            if (!agree(ok, &s_int[1])) break;  // (its barriers also publish s_alpha)
             {
                 T sp = 0;
 #pragma unroll
@@ -317,9 +269,7 @@ __global__ __launch_bounds__(NT) void backsolve_chain_kernel(Args<T> a) {
         }
         __syncthreads();
         if (t < DB) st_sc1(a.alpha + (r0 + t) * a.m + r, s_part[0][t] + s_part[1][t] + s_part[2][t] + s_part[3][t]);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (w == 0) __hip_atomic_store(fl + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        publish_flag(fl + k, 1);
         if (a.trace && r == 0 && t == 0) a.trace[4 * k + 3] = wall_clock64();
     }
     if (t == 0 && ld_uni(a.ctl + C_ERR)) atomicMin(a.info, -1);
@@ -342,13 +292,7 @@ __global__ __launch_bounds__(NT) void forward_chain_kernel(Args<T> a) {
     const int t = threadIdx.x, w = __builtin_amdgcn_readfirstlane(t >> 6), lane = t & 63;
     const int nb = (int)(a.np / DB);
     int* flags = a.ctl + C_NCTL;
-    if (w == 0) {
-        const int v = __hip_atomic_fetch_add(a.ctl + C_TICKET, (t == 0) ? 1 : 0, __ATOMIC_RELAXED,
-                                             __HIP_MEMORY_SCOPE_AGENT);
-        s_int[0] = __builtin_amdgcn_readfirstlane(v);
-    }
-    __syncthreads();
-    const int k = __builtin_amdgcn_readfirstlane(s_int[0]);
+    const int k = claim_ticket(a.ctl, &s_int[0]);
     if (k >= nb) return;
     T* zrows = const_cast<T*>(a.A) + a.np;  // label rows: element (rhs r, sample i) at zrows[r + i ld]
     typedef T v2 __attribute__((ext_vector_type(2)));
@@ -372,14 +316,10 @@ __global__ __launch_bounds__(NT) void forward_chain_kernel(Args<T> a) {
                 p1 = fma(x[cc][1], zc, p1);
             }
         }
-        // agree on a failed wait (each wave polled on its own)
-        if (t == 0) s_int[1] = 0;
-        __syncthreads();
-        if (!ok) s_int[1] = 1;  // (any lane: the alpha poll fails per lane)
         s_part[w][2 * lane] = p0;
         s_part[w][2 * lane + 1] = p1;
-        __syncthreads();
-        if (s_int[1]) {
+        // agree on a failed wait (each wave polled on its own; the barriers also publish s_part)
+        if (!agree(ok, &s_int[1])) {
             ok = false;
             break;
         }
@@ -411,25 +351,16 @@ __global__ __launch_bounds__(NT) void forward_chain_kernel(Args<T> a) {
             for (int ww = 0; ww < 8; ww++) acc += s_part[ww][t];
             st_sc1(zrows + r + ((int64_t)k * DB + t) * a.ld, acc);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (w == 0) __hip_atomic_store(fl + k, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        publish_flag(fl + k, 1);
     }
     if (t == 0 && ld_uni(a.ctl + C_ERR)) atomicMin(a.info, -1);
 }
 
 }  // namespace bs
 
-// GPRX_BS_TRACE timeline of the last launch (per block, 100 MHz wall clock)
-static long long* g_bs_trace = nullptr;
-static int g_bs_trace_n = 0;
-int64_t bs_trace_copy(long long* out, int64_t max_blocks) {
-    if (!g_bs_trace) return 0;
-    const int64_t n = std::min<int64_t>(max_blocks, g_bs_trace_n);
-    GPRX_HIP(hipDeviceSynchronize());
-    GPRX_HIP(hipMemcpy(out, g_bs_trace, sizeof(long long) * 4 * n, hipMemcpyDeviceToHost));
-    return n;
-}
+// GPRX_BS_TRACE timeline of the last launch
+static BlockTrace g_bs_trace;
+int64_t bs_trace_copy(long long* out, int64_t max_blocks) { return g_bs_trace.copy(out, max_blocks); }
 
 template <typename T>
 void launch_backsolve_chain(const T* A, int64_t ld, int64_t np, int m, const T* Linv, T* alpha, int* info,
@@ -455,19 +386,12 @@ void launch_backsolve_chain(const T* A, int64_t ld, int64_t np, int m, const T* 
     a.alpha = alpha;
     a.ctl = scratch;
     a.info = info;
-    a.tlimit = (long long)(1e8 * 4.0);
+    a.tlimit = CHAIN_TLIMIT_TICKS;
     a.trace = nullptr;
     a.tiles = tiles;
     a.tld = tld;
     static const bool tracing = std::getenv("GPRX_BS_TRACE") != nullptr;
-    if (tracing) {
-        if (g_bs_trace_n < nb) {
-            if (g_bs_trace) GPRX_HIP(hipFree(g_bs_trace));
-            GPRX_HIP(hipMalloc(&g_bs_trace, sizeof(long long) * 4 * nb));
-        }
-        g_bs_trace_n = nb;
-        a.trace = g_bs_trace;
-    }
+    if (tracing) a.trace = g_bs_trace.ensure(nb);
     static bool attr = false;
     if (!attr) {
         GPRX_HIP(hipFuncSetAttribute((const void*)backsolve_chain_kernel<double>,
@@ -498,7 +422,7 @@ void launch_forward_chain(T* A, int64_t ld, int64_t np, int m, const T* Linv, in
     a.Linv = Linv;
     a.ctl = scratch;
     a.info = info;
-    a.tlimit = (long long)(1e8 * 4.0);
+    a.tlimit = CHAIN_TLIMIT_TICKS;
     hipLaunchKernelGGL(forward_chain_kernel<T>, dim3((unsigned)nb), dim3(NT), 0, s, a);
     GPRX_HIP(hipGetLastError());
 }

@@ -22,14 +22,13 @@
 // substitution, first block first for the forward one, so a workgroup waits only on blocks
 // claimed before it, on every rank).  A block no rank of this launch works on is still
 // waited for (its alpha / z arrives by push), so the launch ends with the whole vector here.
-// Hand-off: every data store to a mailbox is a system-scope relaxed store (`sc0 sc1`: written
-// through, the line dropped from this XCD's L2) and every read of pushed data a system-scope load,
-// so a flag needs only each storing wave's s_waitcnt vmcnt(0) and a barrier before it -- no L2
-// write-back fence per block (MI355X_MICROARCH.md, inter-workgroup visibility, the {sc0 sc1
-// stores and loads both sides} form; a buffer_wbl2 costs 1.7-6.5 us, on the chain once per
-// block).  The diagonal inverse of the block sits in LDS (loaded before any wait); waits are
-// bounded in wall-clock time.
+// Hand-off: the protocol of k_handoff.h in its cross-rank form -- every data store to a mailbox
+// is st_nc and every read of pushed data ld_nc (the {sc0 sc1 stores and loads both sides} form),
+// the flags are system-scope words in the mailboxes, so a flag needs no L2 write-back fence per
+// block (a buffer_wbl2 costs 1.7-6.5 us, on the chain once per block).  The diagonal inverse of
+// the block sits in LDS (loaded before any wait).
 #include "gprx_dist.h"
+#include "k_handoff.h"
 #include "k_mma.h"
 
 #include <algorithm>
@@ -39,24 +38,10 @@
 namespace gprx {
 namespace ds {
 
+using namespace ho;
+
 constexpr int NT = 512;     // 8 waves
 constexpr int QR = DB / 4;  // rows per thread in the column layout (thread: column t & 127, quarter t >> 7)
-enum { C_TICKET = 0, C_ERR = 1, C_NCTL = 4 };
-
-__device__ __forceinline__ unsigned ld_sys(const unsigned* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void st_sys(unsigned* p, unsigned v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-template <typename T>
-__device__ __forceinline__ T ld_nc(const T* p) {  // data another rank pushed (bypass stale lines)
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-template <typename T>
-__device__ __forceinline__ void st_nc(T* p, T v) {  // data for another workgroup or rank (written through)
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 constexpr int LSL = DB + 1;  // LDS column stride of the diagonal inverse (conflict-free row and column reads)
 // Linv block (column-major, DB x DB) into LDS with stride LSL: coalesced global reads
 template <typename T>
@@ -74,16 +59,7 @@ __device__ __forceinline__ uint64_t uni64(uint64_t v) {
 
 // Wait (every wave on its own) until *f == ep; false on timeout or another workgroup's error.
 __device__ bool wait_eq(const unsigned* f, unsigned ep, int* ctl, long long t0, long long tlimit) {
-    while (__builtin_amdgcn_readfirstlane(ld_sys(f)) != ep) {
-        if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(ctl + C_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)))
-            return false;
-        if (wall_clock64() - t0 > tlimit) {
-            __hip_atomic_store(ctl + C_ERR, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
-    return true;
+    return wait_until([=] { return __builtin_amdgcn_readfirstlane(ld_sys(f)) == ep; }, ctl + C_ERR, t0, tlimit);
 }
 
 template <typename T>
@@ -102,12 +78,10 @@ __device__ __forceinline__ unsigned* mb_flag(const uint64_t* mb, int q, int64_t 
 // the mailboxes) = ep at every rank in mask
 template <typename T>
 __device__ void signal(const DSArgs<T>& a, unsigned mask, int64_t fo, unsigned ep) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if ((threadIdx.x >> 6) == 0) {
+    publish_by([&] {
         for (int q = 0; q < a.g; q++)
             if ((mask >> q) & 1) st_sys(mb_flag(a.mb, q, fo), ep);
-    }
+    });
 }
 
 // z(rhs r, column c) of block k as the back substitution's right-hand side
@@ -125,15 +99,10 @@ __global__ __launch_bounds__(NT) void dist_back_kernel(DSArgs<T> a) {
     T* sL = reinterpret_cast<T*>(s_dyn);  // Linv_k, stride LSL
     const int t = threadIdx.x, lane = t & 63;
     const int c = t & (DB - 1), qq = t >> 7;
-    if ((t >> 6) == 0) {
-        const int v = __hip_atomic_fetch_add(a.ctl + C_TICKET, (t == 0) ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_int[0] = __builtin_amdgcn_readfirstlane(v);
-        // no line of an earlier solve's mailbox traffic (or right-hand side) left in this CU's
-        // or this XCD's caches: the plain loads below (Linv, rhs, own tiles) see this solve's data
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    }
-    __syncthreads();
-    const int tk = __builtin_amdgcn_readfirstlane(s_int[0]);
+    // no line of an earlier solve's mailbox traffic (or right-hand side) left in this CU's
+    // or this XCD's caches: the plain loads below (Linv, rhs, own tiles) see this solve's data
+    if ((t >> 6) == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    const int tk = claim_ticket(a.ctl, &s_int[0]);
     if (tk >= a.nc) return;
     const int k = a.nc - 1 - tk;
     const int ok_ = a.own[k];
@@ -238,7 +207,7 @@ __global__ __launch_bounds__(NT) void dist_back_kernel(DSArgs<T> a) {
         ok = wait_eq(mb_flag(a.mb, a.r, a.o_sflags + 4 * (int64_t)k), a.sep, a.ctl, t0, a.tlimit);
     }
 done:
-    if (t == 0 && __hip_atomic_load(a.ctl + C_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(a.info, -1);
+    if (t == 0 && ld_agent(a.ctl + C_ERR)) atomicMin(a.info, -1);
 }
 
 // z_i = Linv_i (rhs_i - sum_{k < i} L_ik z_k) on own(i); thread: row (t & 127) of block i,
@@ -252,15 +221,10 @@ __global__ __launch_bounds__(NT) void dist_forward_kernel(DSArgs<T> a) {
     T* sL = reinterpret_cast<T*>(s_dyn);  // Linv_i, stride LSL
     const int t = threadIdx.x, lane = t & 63;
     const int row = t & (DB - 1), cq = t >> 7;
-    if ((t >> 6) == 0) {
-        const int v = __hip_atomic_fetch_add(a.ctl + C_TICKET, (t == 0) ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_int[0] = __builtin_amdgcn_readfirstlane(v);
-        // no line of an earlier solve's mailbox traffic (or right-hand side) left in this CU's
-        // or this XCD's caches: the plain loads below (Linv, rhs, own tiles) see this solve's data
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-    }
-    __syncthreads();
-    const int i = __builtin_amdgcn_readfirstlane(s_int[0]);
+    // no line of an earlier solve's mailbox traffic (or right-hand side) left in this CU's
+    // or this XCD's caches: the plain loads below (Linv, rhs, own tiles) see this solve's data
+    if ((t >> 6) == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+    const int i = claim_ticket(a.ctl, &s_int[0]);
     if (i >= a.nc) return;
     const long long t0 = wall_clock64();
     const unsigned all = ((1u << a.g) - 1u);
@@ -313,7 +277,7 @@ __global__ __launch_bounds__(NT) void dist_forward_kernel(DSArgs<T> a) {
     } else {
         ok = wait_eq(mb_flag(a.mb, a.r, a.o_sflags + 4 * ((int64_t)a.nc + i)), a.sep, a.ctl, t0, a.tlimit);
     }
-    if (t == 0 && __hip_atomic_load(a.ctl + C_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(a.info, -1);
+    if (t == 0 && ld_agent(a.ctl + C_ERR)) atomicMin(a.info, -1);
 }
 
 // out[0] = 2 sum log L_ii over this rank's diagonal blocks (global index < n); out[1] = sum of
@@ -375,12 +339,7 @@ __global__ __launch_bounds__(NT) void dist_pvar_kernel(PVArgs<T> a) {
     const unsigned* vf0 = nullptr;
     bool ok = true;
     for (;;) {
-        if (w == 0) {
-            const int v = __hip_atomic_fetch_add(a.ctl + C_TICKET, (t == 0) ? 1 : 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            s_int[0] = __builtin_amdgcn_readfirstlane(v);
-        }
-        __syncthreads();
-        const int tk = __builtin_amdgcn_readfirstlane(s_int[0]);
+        const int tk = claim_ticket(a.ctl, &s_int[0]);
         if (tk >= a.nown * a.nch || !ok) break;
         const int li = tk / a.nch, c = tk - li * a.nch;
         const int i = __builtin_amdgcn_readfirstlane(a.orows[li]);
@@ -396,21 +355,16 @@ __global__ __launch_bounds__(NT) void dist_pvar_kernel(PVArgs<T> a) {
             if (w == 0) {
                 const int nmax = min(64, i - k0);
                 const long long t0 = wall_clock64();
-                int nk = 0;
-                for (;;) {
-                    const bool good = lane >= nmax || ld_sys(vf0 + k0 + (lane < nmax ? lane : 0)) == a.ep;
-                    const unsigned long long bad = __ballot(!good);
-                    nk = bad ? (int)__builtin_ctzll(bad) : nmax;  // the ready prefix
-                    nk = __builtin_amdgcn_readfirstlane(nk);
-                    if (nk > 0) break;
-                    if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(a.ctl + C_ERR, __ATOMIC_RELAXED,
-                                                                         __HIP_MEMORY_SCOPE_AGENT))) break;
-                    if (wall_clock64() - t0 > a.tlimit) {
-                        __hip_atomic_store(a.ctl + C_ERR, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(1);
-                }
+                int nk = 0;  // (stays 0 when the wait fails)
+                wait_until(
+                    [&] {
+                        const bool good = lane >= nmax || ld_sys(vf0 + k0 + (lane < nmax ? lane : 0)) == a.ep;
+                        const unsigned long long bad = __ballot(!good);
+                        nk = bad ? (int)__builtin_ctzll(bad) : nmax;  // the ready prefix
+                        nk = __builtin_amdgcn_readfirstlane(nk);
+                        return nk > 0;
+                    },
+                    a.ctl + C_ERR, t0, a.tlimit);
                 // pushed data: no stale line of an earlier use of the window in this CU's or XCD's caches
                 if (nk > 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
                 s_int[1] = nk;
@@ -440,8 +394,7 @@ __global__ __launch_bounds__(NT) void dist_pvar_kernel(PVArgs<T> a) {
                     T* p = Wt + q + (int64_t)m * ldr;
                     *p = *p - acc[x][y][reg];
                 }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        local_sync();
         // V_i(c)(r, q) = sum_m Linv_i(r, m) W(q, m)
         mm::tile_mma<T>(acc, a.Linv + (int64_t)i * DB * DB, DB, Wt, ldr, DB, DB, smem, t);
         __syncthreads();  // ring done: the LDS takes V (q + r VS)
@@ -479,12 +432,11 @@ __global__ __launch_bounds__(NT) void dist_pvar_kernel(PVArgs<T> a) {
                     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(d4 + t + u * NT), "v"(v[u]) : "memory");
             }
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (w == 0)
+        publish_by([&] {
             for (int q = 0; q < a.g; q++) st_sys(mb_flag(a.mb, q, a.o_vflags + 4 * ((int64_t)c * a.nc + i)), a.ep);
+        });
     }
-    if (t == 0 && __hip_atomic_load(a.ctl + C_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(a.info, -1);
+    if (t == 0 && ld_agent(a.ctl + C_ERR)) atomicMin(a.info, -1);
 }
 
 }  // namespace ds

@@ -13,6 +13,7 @@
 // orow(lk, reg)) with w = wave, wr = w & 1, wc = w >> 1, lr = lane & 15, lk = lane >> 4.
 #pragma once
 #include "gprx_internal.h"
+#include "k_handoff.h"
 
 namespace gprx {
 namespace mm {
@@ -163,10 +164,7 @@ constexpr size_t gemm_lds() {  // (the larger of the two stage depths a launch m
                                                                                   : NBUF * Stage<T, BKS>::STG);
 }
 
-template <typename T>
-__device__ __forceinline__ void st_sc1(T* p, T v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // global_store ... sc1
-}
+using ho::st_sc1;  // global_store ... sc1
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {

@@ -39,6 +39,7 @@
 // keeps the launch at one workgroup per CU, so the critical DIAGX step has a whole CU.
 #include "gprx_dist.h"
 #include "gprx_internal.h"
+#include "k_handoff.h"
 #include "k_pairs.h"
 
 #include <algorithm>
@@ -56,6 +57,17 @@ namespace gprx {
 namespace pt {
 
 using namespace mm;
+// the hand-off helpers (k_handoff.h) by name: this file keeps its own control-word layout (mm::C_*)
+using ho::ld_agent;
+using ho::ld_sys;
+using ho::ld_uni;
+using ho::local_sync;
+using ho::publish;
+using ho::publish2;
+using ho::st_agent;
+using ho::st_sys;
+using ho::wait_until;
+using ho::wave_id;
 static_assert(C_NCTL == C_NCTL_DIST, "counter block layout shared with gprx_dist.cpp");
 
 // ------------------------------------------------------------------------------------------
@@ -194,8 +206,6 @@ __device__ __forceinline__ void tile_gemm_tall(T* __restrict__ C, int64_t ldc, c
 // ------------------------------------------------------------------------------------------
 constexpr int SPL = DB + 4;
 constexpr int SIL = DB + 2;
-
-__device__ __forceinline__ void st_agent(int* p, int v);  // (hand-off helpers, below)
 
 // v_rsq_f64 (relative error ~2^-23) refined by ONE Halley step, y (1 + e/2 + 3e^2/8) with
 // e = 1 - x y^2 (cubic convergence: error ~2^-69 before rounding): 4 dependent f64 operations
@@ -1240,7 +1250,6 @@ constexpr bool DIAG_LA = false;
 // spill reload inside the update mainloop broke its counted vmcnt pipelining)
 // pub (optional): publish *pub = pub_v when the block is stored, inside the call -- the
 // callee-saved registers are restored after it (scratch loads), not before the chain goes on
-__device__ __forceinline__ void publish(int* flag, int v, bool release);
 template <typename T>
 __device__ __noinline__ void diag_factor(T* __restrict__ A, int64_t ld, T* __restrict__ Linv, int* __restrict__ info,
                                          int64_t col0, unsigned char* smem_raw, const int t, int* dbg = nullptr,
@@ -1299,50 +1308,6 @@ void launch_diag_bench(int variant, T* A, int64_t ld, T* Linv, int* info, long l
 template void launch_diag_bench<double>(int, double*, int64_t, double*, int*, long long*, int, hipStream_t);
 template void launch_diag_bench<float>(int, float*, int64_t, float*, int*, long long*, int, hipStream_t);
 
-// ------------------------------------------------------------------------------------------
-// Hand-off helpers
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int ld_agent(const int* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_agent(int* p, int v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// every wave's stores complete, then wave 0 releases and publishes *flag = v.  Wave 0 acts
-// with ALL its lanes (same value to the same word): no lane-divergent code near the task
-// loop's back edge, where the structurizer was seen to sink a `lane == 0` block past the
-// next iteration's barrier (a hang).
-__device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
-
-// release = false: every handed-off byte was stored sc1 (tile_gemm), so draining the stores
-// (vmcnt(0) in every wave, then the barrier) is the release; the consumer still acquires.
-__device__ __forceinline__ void publish(int* flag, int v, bool release) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (wave_id() == 0) {
-        if (release) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        st_agent(flag, v);
-    }
-}
-
-// two counters after one drain (a paired update's tiles)
-__device__ __forceinline__ void publish2(int* f1, int* f2, int v) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (wave_id() == 0) {
-        st_agent(f1, v);
-        st_agent(f2, v);
-    }
-}
-
-// stores of this workgroup visible to its own later loads (same CU)
-__device__ __forceinline__ void local_sync() {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-}
-
 template <typename T>
 constexpr size_t pt_lds_bytes() {
     return gemm_lds<T>() > diag_lds<T>() ? gemm_lds<T>() : diag_lds<T>();
@@ -1380,18 +1345,6 @@ struct Args {
                  // stored; [TP_DPAN] DIAGX(k)'s published panels
 };
 
-
-// Wave 0 waits until the task's inputs are final (all lanes load the same words; the values
-// are made wave-uniform, so the loop is a scalar loop with no divergence).  Returns false on
-// timeout or when another workgroup raised the error flag.
-__device__ __forceinline__ int ld_uni(const int* p) { return __builtin_amdgcn_readfirstlane(ld_agent(p)); }
-// flag words another rank stores into this rank's mailbox: system scope
-__device__ __forceinline__ unsigned ld_sys(const unsigned* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-__device__ __forceinline__ void st_sys(unsigned* p, unsigned v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
 
 // A timed-out wait of the distributed factorisation leaves one record (the first) at
 // check_err[DIST_TO_REC..+7]: kind (1 inputs, 2 window release), task type, i, j, b0 | nb << 16,
@@ -1470,15 +1423,12 @@ __device__ bool dist_wait_release(const Args<T>& a, const PtDist<T>& D, unsigned
     for (int q = 0; q < D.g; q++) {
         if (!((mask >> q) & 1) || __builtin_amdgcn_readfirstlane(D.need[(int64_t)q * D.nc + p]) == 0) continue;
         unsigned seen;
-        while ((seen = __builtin_amdgcn_readfirstlane(ld_sys(fl + (int64_t)q * D.nc + p))) != D.ep) {
-            if (ld_uni(a.ctl + C_ERR)) return false;
-            if (wall_clock64() - t0 > a.tlimit) {
-                if ((threadIdx.x & 63) == 0) dist_note_timeout(D.check_err + DIST_TO_REC, 2, -1, D.r, p, 0, q, (int)seen);
-                st_agent(a.ctl + C_ERR, 1);
-                return false;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
+        if (!wait_until<2>([&] { return (seen = __builtin_amdgcn_readfirstlane(ld_sys(fl + (int64_t)q * D.nc + p))) == D.ep; },
+                           a.ctl + C_ERR, t0, a.tlimit, [&] {
+                               if ((threadIdx.x & 63) == 0)
+                                   dist_note_timeout(D.check_err + DIST_TO_REC, 2, -1, D.r, p, 0, q, (int)seen);
+                           }))
+            return false;
     }
     return true;
 }
@@ -1581,6 +1531,9 @@ __device__ void dist_release(const PtDist<T>& D, int b0, int nb) {
     }
 }
 
+// Wave 0 waits until the task's inputs are final (all lanes load the same words; the values
+// are made wave-uniform, so the loop is a scalar loop with no divergence).  Returns false on
+// timeout or when another workgroup raised the error flag.
 template <typename T, bool DIST>
 __device__ bool wait_inputs(const Args<T>& a, int type, int i, int j, int b0, int nb) {
     const int* vp;
@@ -1902,15 +1855,7 @@ __device__ bool tpart_wait_linv(const TpCtx<T>& a, int kk, bool& remote) {
 template <typename T>
 __device__ bool tpart_wait_ver(const TpCtx<T>& a, const int* v, int want) {
     const long long t0 = wall_clock64();
-    for (;;) {
-        if (ld_uni(v) == want) return true;
-        if (ld_uni(a.ctl + C_ERR)) return false;
-        if (wall_clock64() - t0 > a.tlimit) {
-            st_agent(a.ctl + C_ERR, 1);
-            return false;
-        }
-        __builtin_amdgcn_s_sleep(1);
-    }
+    return wait_until([&] { return ld_uni(v) == want; }, a.ctl + C_ERR, t0, a.tlimit);
 }
 
 // wave 0: lane l < n checks f[l] >= want (one vector load, one ballot per poll)
