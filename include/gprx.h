@@ -63,7 +63,15 @@ typedef enum gprx_dtype { GPRX_F32 = 0, GPRX_F64 = 1 } gprx_dtype;
  *   WHITE             p = (scale)               include/Kernel.h:717-720
  *   RATIONAL_QUADRATIC p = (scale, sigma, alpha) include/Kernel.h:812-819
  *   PERIODIC          p = (scale, b, sigma)     include/Kernel.h:950-960
- *   SUM / PRODUCT     gradient = [k1 params, k2 params] include/Kernel.h:169-178, 318-327 */
+ *   SUM / PRODUCT     gradient = [k1 params, k2 params] include/Kernel.h:169-178, 318-327
+ * The device evaluates a tree expanded into a sum of products of its leaves, within these
+ * limits: at most 8 leaves, at most 16 product terms after the expansion (checked at every
+ * SUM and PRODUCT node) and at most 2 PERIODIC leaves.  A tree beyond one of them is refused with
+ * GPRX_ERR_ARG wherever a descriptor is taken (it can still be used as a kernel with no device
+ * form, below).  Trees with one PERIODIC leaf at most and no WHITE leaf build their
+ * covariance from MFMA pair statistics, and so does their mean prediction for one label
+ * column (m = 1); the other trees (two PERIODIC leaves among them), every prediction
+ * with derivatives and every mean prediction with m > 1 take the direct kernels. */
 typedef enum gprx_kop {
     GPRX_K_GAUSSIAN = 1,
     GPRX_K_GAUSSIAN_EXP = 2,
@@ -200,7 +208,10 @@ gprx_status gprx_model_set_noise(gprx_model* model, double sigma);
                                       solve sharded the same way, no N^2 on any rank) and the LML
                                       (value and gradient, GPRX_LML_DISTRIBUTED) run on it; the core
                                       matrix gathers the dense factor onto each process (the
-                                      reference returns all of C) */
+                                      reference returns all of C).  The labels ride along as one
+                                      128-row block: at most 128 label columns (m), GPRX_ERR_DIM
+                                      beyond; the single-GPU fit, gprx_model_append and
+                                      gprx_sparse_fit take any m */
 #define GPRX_FIT_F32_NO_REFINE 4u  /* fp32 models: skip the fp64 iterative refinement of alpha.  By
                                       default an fp32 fit factorises in fp32 and refines alpha in
                                       fp64 until it agrees with the double solve: the reference
