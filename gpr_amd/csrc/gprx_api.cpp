@@ -920,8 +920,9 @@ static gprx_status model_fit(gprx_model* M, uint32_t flags, gprx_fit_info* out) 
     }
     GPRX_HIP(hipEventRecord(ctx->ev[1], s));
     if (tb.mode || want_inv) {
+        // (the label block's live rows: with m <= 16 its updates skip the zero padding)
         potrf_tiles<T>(M->A.as<T>(), ld, np, ld, M->Linv.as<T>(), M->info.as<int>(), ctx->ex, tb.mode ? &tb : nullptr,
-                       want_inv ? (int)(np / GT) : 0);
+                       want_inv ? (int)(np / GT) : 0, false, mp == GT ? M->m : GT);
     } else {
         potrf_auto<T>(M->A.as<T>(), ld, np, ld, M->Linv.as<T>(), M->info.as<int>(), ctx->ex);
     }

@@ -575,9 +575,11 @@ TileBuild<T> pairs_tile_build(const KCanon<T>& K, const KCanon<T>* Kd, const T* 
 // L^{-T} (upper triangular, ni = np / 128): the inverse factor riding along as extra rows,
 // each identity block updated only from its own column block on.
 // build_only: run the BUILD tasks alone (the covariance tiles, no factorisation; parity hook).
+// lab_live: the live rows of the label row block (the rows below them are stored zeros); with one
+// label row block and at most 16 live rows its updates compute those 16 rows only.  GT: all.
 template <typename T>
 void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info, Exec& ex,
-                 const TileBuild<T>* build = nullptr, int ni = 0, bool build_only = false);
+                 const TileBuild<T>* build = nullptr, int ni = 0, bool build_only = false, int lab_live = GT);
 // C (lower) = A B^T where both operands vanish left of their row (LAUUM shape), k_potrf.hip
 template <typename T>
 void launch_gemm_nt_kskip(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t M, int64_t N,
@@ -587,7 +589,8 @@ template <typename T>
 void potrf_auto(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info, Exec& ex);
 bool potrf_uses_tiles();
 int64_t potrf_tiles_schedule_stats(int nc, int nr, int P, bool build, double* est_us, int ni = 0, int ratio = -1,
-                                   int32_t* list_out = nullptr, int64_t list_max = 0, int pair = -1);
+                                   int32_t* list_out = nullptr, int64_t list_max = 0, int pair = -1,
+                                   bool narrow = false);
 // Generic C = beta C + alpha A B^T on GT-multiples (column-major).  lower: only tiles
 // with col-tile <= row-tile are computed, and inside diagonal tiles only row >= col.
 template <typename T>

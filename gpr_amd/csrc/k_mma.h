@@ -542,6 +542,85 @@ __device__ __forceinline__ void tile_mma_trirows(typename Mfma<T>::acc_t (&acc)[
     if constexpr (NST > 7) stage(std::integral_constant<int, (NST > 7 ? 7 : 0)>{});
 }
 
+// acc = A B^T for the first 16 rows of A only (a 16 x 128 output; A's other rows are not
+// multiplied) -- the update of a label row block that holds at most 16 labels, whose rows below
+// them are stored zeros and stay zero (0 - 0 B^T).  Wave w owns output columns 16 w .. 16 w + 15:
+// one MFMA per k-step into one accumulator, 1/8 of the full tile's, so the product is bound by its
+// operand feed, not by the MFMA pipe.  The staging ring and Stage<T> layout are tile_mma's (whole
+// 128-row A columns are staged: the rows beyond 16 are never read from LDS), with the plain early
+// barrier (tile_mma's FEED 0).  Per output element the MFMA steps and their k order are the ones
+// the full tile performs (f32: the PAIRED column order of the 32-deep stages), so the 16 rows
+// come out bit for bit as tile_mma computes them.
+// acc[reg] = C(row = lr, col = 16 w + orow(lk, reg)).
+template <typename T>
+__device__ __forceinline__ void tile_mma_rows16(typename Mfma<T>::acc_t& acc, const T* __restrict__ A, int64_t lda,
+                                                const T* __restrict__ B, int64_t ldb, int K, T* smem, const int t) {
+    typedef Mfma<T> Tr;
+    typedef typename Tr::acc_t acc_t;
+    constexpr int BK = BkOf<T>::v;
+    typedef Stage<T, BK> S;
+    const int lane = t & 63, w = t >> 6;
+    const int lr = lane & 15, lk = lane >> 4;
+    const int lcol = lane / S::LPC, lrow = S::src_row(lane);
+    auto issue = [&](int st) {
+        T* buf = smem + (st % S::NB) * S::STG;
+#pragma unroll
+        for (int u = 0; u < S::IPW; u++) {
+            const int g = w * S::IPW + u;
+            const bool isB = g >= S::GRP;
+            const int gg = isB ? g - S::GRP : g;
+            const int64_t col = (int64_t)st * BK + gg * S::CPI + lcol;
+            const T* src = isB ? (B + lrow + col * ldb) : (A + lrow + col * lda);
+            __builtin_amdgcn_global_load_lds((const void*)src,
+                                             (__attribute__((address_space(3))) void*)(buf + g * S::SRP), 16, 0, 0);
+        }
+    };
+    acc = acc_t{0};
+    const int nst = __builtin_amdgcn_readfirstlane(K) / BK;
+#pragma unroll
+    for (int p = 0; p < S::AH; p++)
+        if (p < nst) issue(p);
+#pragma nounroll
+    for (int st = 0; st < nst; st++) {
+        const int ahead = nst - 1 - st;
+        if (S::AH >= 3 && ahead >= 2) wait_vm<(S::AH >= 3 ? 2 : 0) * S::IPW>();
+        else if (S::AH >= 2 && ahead >= 1) wait_vm<S::IPW>();
+        else wait_vm<0>();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        if (st + S::AH < nst) issue(st + S::AH);
+        const T* a = smem + (st % S::NB) * S::STG;
+        const T* b = a + S::GRP * S::SRP;
+        constexpr bool PAIRED = sizeof(T) == 4 && BK >= 32 && S::CPI == 2 && S::ROT == 0;
+        if constexpr (PAIRED) {  // (tile_mma: k-step 2 j + h takes the k-columns 2 (4 j + lk) + h)
+            T pa[BK / 8][2], pb[BK / 8][2];
+#pragma unroll
+            for (int j = 0; j < BK / 8; j++) {
+                const T* ac = a + (4 * j + lk) * S::SRP;
+                const T* bc = b + (4 * j + lk) * S::SRP;
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    pa[j][h] = ac[h * GT + lr];
+                    pb[j][h] = bc[h * GT + 16 * w + lr];
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < BK / 8; j++)
+#pragma unroll
+                for (int h = 0; h < 2; h++) acc = Tr::mma(pb[j][h], pa[j][h], acc);
+        } else {
+            T fa[BK / 4], fb[BK / 4];
+#pragma unroll
+            for (int kq = 0; kq < BK / 4; kq++) {
+                fa[kq] = a[S::at(kq * 4 + lk, lr)];
+                fb[kq] = b[S::at(kq * 4 + lk, 16 * w + lr)];
+            }
+#pragma unroll
+            for (int kq = 0; kq < BK / 4; kq++) acc = Tr::mma(fb[kq], fa[kq], acc);
+        }
+    }
+}
+
 // 256 x 128 output tile (A: 256 rows, B: 128 rows), for stand-alone kernels only: 128
 // accumulator registers, which the factorisation's task loop (at 256 VGPRs) cannot hold.  The 8
 // waves take 4 x 2 blocks of 64 x 64: 16 MFMAs per k-step from 8 fragment reads (the 128 x 128

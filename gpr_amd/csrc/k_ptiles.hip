@@ -158,6 +158,26 @@ __device__ __forceinline__ void tile_trsm(T* C, int64_t ldc, const T* A, int64_t
     }
 }
 
+// Narrow label-row update: C -= A B^T for rows 0..15 of the tile only (k_mma.h tile_mma_rows16) --
+// the label row block of a fit with at most 16 labels, whose other rows are stored zeros that the
+// full tile would multiply (0 - 0 B^T) for nothing.  Wave w: the 16 rows x columns 16 w .. 16 w +
+// 15; C - acc goes out in sc1 stores as tile_gemm<T, true> does it, the same MFMA steps in the
+// same k order before the same subtraction, so the live rows keep their bits.  Rows 16..127 of
+// the tile are neither read nor written.
+template <typename T>
+__device__ __forceinline__ void tile_gemm_rows16(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int64_t lda,
+                                                 const T* __restrict__ B, int64_t ldb, int K, T* smem, const int t) {
+    typedef Mfma<T> Tr;
+    const int lane = t & 63, w = t >> 6, lr = lane & 15, lk = lane >> 4;
+    T cv[4];
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++) cv[reg] = C[(int64_t)(16 * w + Tr::orow(lk, reg)) * ldc + lr];
+    typename Tr::acc_t acc;
+    mm::tile_mma_rows16<T>(acc, A, lda, B, ldb, K, smem, t);
+#pragma unroll
+    for (int reg = 0; reg < 4; reg++) st_sc1(C + (int64_t)(16 * w + Tr::orow(lk, reg)) * ldc + lr, cv[reg] - acc[reg]);
+}
+
 // ------------------------------------------------------------------------------------------
 // Paired update (T_UPD2): C -= A B^T on a 256 x 128 tile -- tiles (i, j) and (i + 1, j), which
 // are adjacent rows of the column-major factor (C and A are 256 rows at one ld) -- over K panels
@@ -1343,7 +1363,10 @@ struct Args {
     T* pbuf;     // DB x DB: S, its lower tiles written by the parts
     int* tflag;  // [nc][TP_STRIDE] TPART(k, p) state: 1 its A operand is read, 2 its T stored, 3 its S quarter
                  // stored; [TP_DPAN] DIAGX(k)'s published panels
+    int lab_rows;  // live rows of the label row block nc (one GPU): <= LAB_NARROW, its updates take
+                   // the 16-row product (tile_gemm_rows16); GT = the full tile
 };
+constexpr int LAB_NARROW = 16;
 
 
 // A timed-out wait of the distributed factorisation leaves one record (the first) at
@@ -2571,9 +2594,14 @@ __global__ __launch_bounds__(NT) void potrf_tiles_kernel(Args<T> a) {
             // variant 128 (timing experiment, wrong results): operand stride 0 along k, every
             // k-slice of the update re-reads the same 1 KB column -- a truly cache-resident feed
             const int64_t lop = (a.variant & 128) ? 0 : ld;
-            if (!(a.variant & 2))
+            // (the narrow label row is a call of its own, not a row bound inside tile_mma's mainloop)
+            if (a.variant & 2) {  // (timing experiment: no update math)
+            } else if (i == a.nc && a.lab_rows <= LAB_NARROW) {
+                tile_gemm_rows16<T>(Ci + (int64_t)j * GT * ld, ld, a.A + oa, lop, a.A + ob, lop, nb * GT, smem, tid);
+            } else {
                 tile_gemm<T, true>(Ci + (int64_t)j * GT * ld, ld, a.A + oa, lop, a.A + ob, lop, nb * GT, i == j, smem,
                                    tid);
+            }
             publish(a.ver + (int64_t)i * a.nv + j, b0 + nb, false);
         } else if (type == T_UPD2) {  // tiles (i, j) and (i + 1, j): one 256 x 128 update
             if (!(a.variant & 2))
@@ -2662,6 +2690,11 @@ struct Cost {  // per-task durations (us, one CU), calibrated from GPRX_PT_TRACE
     // which chunks pair (make_schedule pair > 0): at least pair_nbmin panels wide, in the columns
     // before the last pair_tail (GPRX_PT_PAIR_NBMIN / GPRX_PT_PAIR_TAIL)
     int pair_nbmin = 1, pair_tail = 0;
+    // per 128-deep slice of a narrow label-row update (make_schedule narrow; GPRX_PT_KLAB_US);
+    // < 0: priced as a full tile's (k128).  C3 fit traces: 4.3-4.5 us per panel against 15.7 for a
+    // full tile (profiles/label_rows_pt_trace_fit16384_narrow*.json); priced so, C3's launch
+    // 24.28-24.30 -> 24.22-24.23 ms, same box, three rounds (profiles/label_rows_ab.txt)
+    double klab = 4.3;
 };
 
 // TPART tickets of one k in the order TPART(k, np-1), .., (k, 0): each part waits for
@@ -2749,11 +2782,17 @@ static void tile_chunks(int i, int j, int W, int near, std::vector<std::pair<int
 // row go in vertical pairs (j + pair, j + pair + 1), ..., each pair's identical chunks as ONE
 // T_UPD2 task (a 256 x 128 update: tile_gemm_tall); the `pair` - 1 tiles right below the
 // diagonal -- the diagonal chain's inputs -- and the identity rows stay single
+// narrow: the label row block nc (the only one) updates as a 16-row product (tile_gemm_rows16).  As
+// the bottom of a pair it would gain nothing -- the pair lasts as long as the waves that hold the
+// matrix row -- so it is never one: the rows i >= nc leave the pairs, row nc - 1 runs single in
+// the columns where it was the label row's top, and the label updates are priced at Cost::klab
 static Schedule make_schedule(int nc, int nr, int W, int near, int P, const Cost& cm0, bool build, int ni = 0,
-                              int ratio = 0, bool split = false, int tail = 0, int pair = 0) {
+                              int ratio = 0, bool split = false, int tail = 0, int pair = 0, bool narrow = false) {
     Cost cm = cm0;
     if (split) cm.early = cm.early_s;
     const int nr0 = nr - ni;
+    narrow = narrow && nr0 == nc + 1;
+    const int pend = narrow ? nc : nr0;  // the matrix-row pairs end before row block pend
     auto start_of = [&](int i) { return i >= nr0 ? i - nr0 : 0; };
     // identity rows in pairs (E_2s, E_2s+1): both update from panel 2s -- the bottom row's block at
     // column 2s is a stored zero (potrf_tiles zeroes it and starts its counters at 2s), so its
@@ -2784,8 +2823,8 @@ static Schedule make_schedule(int nc, int nr, int W, int near, int P, const Cost
             return 2;
         }
         const int r0 = j + pair;
-        if (i >= r0 && (i - r0) % 2 == 0 && i + 1 < nr0) return 1;
-        if (i - 1 >= r0 && (i - 1 - r0) % 2 == 0) return 2;
+        if (i >= r0 && (i - r0) % 2 == 0 && i + 1 < pend) return 1;
+        if (i - 1 >= r0 && (i - 1 - r0) % 2 == 0 && i < pend) return 2;
         return 0;
     };
     std::vector<Task> tasks;
@@ -2888,7 +2927,8 @@ static Schedule make_schedule(int nc, int nr, int W, int near, int P, const Cost
                 last_upd[(size_t)(c.i + 1) * nc + c.j] = id;
                 continue;
             }
-            const double dur = cm.ovh + c.nb * cm.k128 * (c.i == c.j ? cm.diagf : 1.0);
+            const bool lab = narrow && c.i == nc && cm.klab >= 0;
+            const double dur = cm.ovh + c.nb * (lab ? cm.klab : cm.k128 * (c.i == c.j ? cm.diagf : 1.0));
             const int id = add(T_UPD, c.i, c.j, c.b0, c.nb, dur);
             dep(id, last_upd[(size_t)c.i * nc + c.j]);
             bool e1, e2;
@@ -3272,6 +3312,8 @@ struct Params {
     int tail = 0;           // > 0: the capped chunk rule only in the last `tail` column blocks
     int pair = -1;          // paired updates (make_schedule): < 0 the precision's default (default_pair),
                             // 0 off, n > 0 pairs from row j + n (GPRX_PT_PAIR)
+    int label = 1;          // the narrow label row (make_schedule narrow, tile_gemm_rows16) where a fit has
+                            // at most LAB_NARROW labels; GPRX_PT_LABEL=0: the full tile and its pairing (A/B)
     Cost cm;
     int near_for(int nc) const { return near >= 0 ? near : (nc <= 64 ? 1 : 0); }
     Params() {
@@ -3292,6 +3334,8 @@ struct Params {
         if (const char* e = std::getenv("GPRX_PT_TPART_US")) cm.tpart = std::atof(e);
         if (const char* e = std::getenv("GPRX_PT_DIAGXS_US")) cm.diagx_s = std::atof(e);
         if (const char* e = std::getenv("GPRX_PT_TPARTP_US")) cm.tpart_prog = std::atof(e);
+        if (const char* e = std::getenv("GPRX_PT_KLAB_US")) cm.klab = std::atof(e);
+        if (const char* e = std::getenv("GPRX_PT_LABEL")) label = std::atoi(e);
     }
     // the cost model for a precision: the progressive parts are the f64 look-ahead factor's
     Cost cost(bool f64) const {
@@ -3325,7 +3369,8 @@ struct PairRule {
     int pair, nbmin, tail;
 };
 static PairRule default_pair(bool f64) { return f64 ? PairRule{4, 4, 32} : PairRule{2, 4, 16}; }
-static Schedule best_schedule(int nc, int nr, const Params& pr, int P, bool build, int ni, bool split, bool f64) {
+static Schedule best_schedule(int nc, int nr, const Params& pr, int P, bool build, int ni, bool split, bool f64,
+                              bool narrow = false) {
     Cost cm = pr.cost(f64);
     const PairRule pd = default_pair(f64);
     if (!std::getenv("GPRX_PT_PAIR_NBMIN")) cm.pair_nbmin = pd.nbmin;
@@ -3346,13 +3391,13 @@ static Schedule best_schedule(int nc, int nr, const Params& pr, int P, bool buil
             }
         };
         if (pr.ratio >= 0) {
-            consider(make_schedule(nc, nr, pr.W, pr.near_for(nc), P, cm, build, ni, pr.ratio, split, pr.tail, pq));
+            consider(make_schedule(nc, nr, pr.W, pr.near_for(nc), P, cm, build, ni, pr.ratio, split, pr.tail, pq, narrow));
             continue;
         }
         for (int r : kRatios)
             for (int tl : kTails) {
                 if ((r == 0 && tl) || (tl && tl >= nc)) continue;
-                consider(make_schedule(nc, nr, pr.W, pr.near_for(nc), P, cm, build, ni, r, split, tl, pq));
+                consider(make_schedule(nc, nr, pr.W, pr.near_for(nc), P, cm, build, ni, r, split, tl, pq, narrow));
             }
     }
     return best;
@@ -3470,7 +3515,7 @@ __global__ void pt_init_identity_rows(T* __restrict__ A, int64_t ld, int64_t row
 
 template <typename T>
 void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info, Exec& ex, const TileBuild<T>* build,
-                 int ni, bool build_only) {
+                 int ni, bool build_only, int lab_live) {
     using namespace pt;
     if (!ex.pt) ex.pt = new PtState();
     PtState& st = *ex.pt;
@@ -3489,7 +3534,9 @@ void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info
     // build_only (a parity hook, gprx_dev_build_matrix): the ticket list holds the BUILD tasks
     // alone, so the launch writes exactly the covariance tiles the fused factorisation starts from
     const bool split = split_for(std::is_same<T, double>::value, st.ncu);
-    auto key = std::make_tuple(nc, nr, fused, build_only ? -1 : ni, split, (int)sizeof(T));
+    // the narrow label row: one label row block with at most LAB_NARROW live rows (GPRX_PT_LABEL=0: off)
+    const bool narrow = !build_only && lab_live <= LAB_NARROW && nr - ni == nc + 1 && params().label != 0;
+    auto key = std::make_tuple(nc, nr, fused, build_only ? -1 : ni, split, (int)sizeof(T) | (narrow ? 256 : 0));
     auto it = st.sched.find(key);
     if (it == st.sched.end()) {
         const Params& pr = params();
@@ -3498,7 +3545,7 @@ void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info
             for (int i = 0; i < nc; i++)
                 for (int j = 0; j <= i; j++) S.list.push_back(make_int4(T_BUILD, i, j, 0));
         } else {
-            S = best_schedule(nc, nr, pr, st.ncu, fused, ni, split, std::is_same<T, double>::value);
+            S = best_schedule(nc, nr, pr, st.ncu, fused, ni, split, std::is_same<T, double>::value, narrow);
         }
         PtState::Dev d;
         d.n = (int64_t)S.list.size();
@@ -3551,6 +3598,7 @@ void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info
     a.tflag = st.ctr + C_NCTL + nr + (size_t)nr * nc;
     if (split && !st.pbuf) GPRX_HIP(hipMalloc(&st.pbuf, sizeof(T) * 4 * DB * DB));
     a.pbuf = static_cast<T*>(st.pbuf);
+    a.lab_rows = narrow ? lab_live : GT;
     if (fused) {
         GPRX_REQUIRE(build->nf == np, GPRX_ERR_ARG, "potrf_tiles: build features must have np rows");
         if (!st.tb) GPRX_HIP(hipMalloc(&st.tb, sizeof(TileBuild<double>)));
@@ -3651,6 +3699,7 @@ void potrf_tiles_dist_launch(const DistLaunch<T>& L) {
     a.split = L.split;
     a.pbuf = L.pbuf;
     a.tflag = L.tflag;
+    a.lab_rows = GT;  // (the sharded engine's label rows keep the full tile)
     auto lds_of = [](size_t b) { return std::max<size_t>(b, 96 * 1024); };
     const size_t lds = lds_of(pt_lds_total<T>());
     static bool attr = false;
@@ -3670,15 +3719,15 @@ template void potrf_tiles_dist_launch<float>(const DistLaunch<float>&);
 // Host-only schedule statistics (no device work): tasks, predicted makespan, and a check
 // that every task's producers come earlier in the ticket order.
 int64_t potrf_tiles_schedule_stats(int nc, int nr, int P, bool build, double* est_us, int ni, int ratio,
-                                   int32_t* list_out, int64_t list_max, int pair) {
+                                   int32_t* list_out, int64_t list_max, int pair, bool narrow) {
     if (nc < 1 || nr < nc || P < 1 || ni < 0 || ni > nr - nc)
         throw Error{GPRX_ERR_ARG, "potrf tile schedule: need nc >= 1, nr >= nc + ni, P >= 1"};
     pt::Params pr = pt::params();
     if (pair >= 0) pr.pair = pair;
     const bool split = pt::split_for(true, P);  // the f64 schedule
     pt::Schedule S = ratio >= 0 ? pt::make_schedule(nc, nr, pr.W, pr.near_for(nc), P, pr.cost(true), build, ni, ratio, split,
-                                                    pr.tail, pr.pair > 0 ? pr.pair : 0)
-                                : pt::best_schedule(nc, nr, pr, P, build, ni, split, true);
+                                                    pr.tail, pr.pair > 0 ? pr.pair : 0, narrow)
+                                : pt::best_schedule(nc, nr, pr, P, build, ni, split, true, narrow);
     if (est_us) *est_us = S.est_us;
     if (list_out)  // the ticket list: {type | nb << 8, i, j, b0} per ticket
         for (int64_t q = 0; q < (int64_t)S.list.size() && q < list_max; q++) {
@@ -3691,8 +3740,8 @@ int64_t potrf_tiles_schedule_stats(int nc, int nr, int P, bool build, double* es
 bool potrf_split_for(bool f64, int P) { return pt::split_for(f64, P); }
 
 template void potrf_tiles<double>(double*, int64_t, int64_t, int64_t, double*, int*, Exec&, const TileBuild<double>*,
-                                  int, bool);
+                                  int, bool, int);
 template void potrf_tiles<float>(float*, int64_t, int64_t, int64_t, float*, int*, Exec&, const TileBuild<float>*, int,
-                                 bool);
+                                 bool, int);
 
 }  // namespace gprx

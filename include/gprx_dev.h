@@ -26,7 +26,8 @@ gprx_status gprx_dev_bench(gprx_ctx* ctx, gprx_dtype dtype, int32_t what, int64_
                            int32_t iters, double* ms);
 /* Host-only: build the tile-dataflow potrf schedule for nc diagonal blocks, nr row blocks
  * and P workers (build bit 0: with the fused covariance-build tasks; bit 1: the last nc of
- * the nr row blocks are identity rows, the inverse riding along; bits 8..15: the update
+ * the nr row blocks are identity rows, the inverse riding along; bit 2: the narrow label row --
+ * row block nc, the only label block, updates as a 16-row product and leaves the pairs; bits 8..15: the update
  * chunk rule's ratio + 1, 0 = the rule the simulated makespan picks; bits 16..23: the paired
  * updates' first row below the diagonal + 1, 1 = no pairs, 0 = the simulation's choice); returns its task count
  * and simulated makespan (us).  Throws nothing, needs no

@@ -82,6 +82,19 @@ for t in (0, 1, 2, 3, 4, 5):
 res["chip_ms_by_type"] = {names[t]: round(float(ex[typ == t].sum() / P / 1e3), 3) for t in (0, 1, 2, 3, 4, 5)}
 res["chip_ms_wait"] = round(float(wt.sum() / P / 1e3), 3)
 res["chip_ms_idle"] = round(float(span / 1e3 - (ex.sum() + wt.sum()) / P / 1e3), 3)
+# the label row's updates (row block nc of a fit; single tasks, or the bottom of a pair): per-panel
+# time of the single ones by least squares exec = ovh + panels * per_panel, and their chip time
+lab = (typ == 2) & (tasks[:, 1] == nc)
+if lab.sum() > 1:
+    per_panel, ovh = np.polyfit(nb[lab].astype(float), ex[lab], 1) if len(set(nb[lab])) > 1 else (float("nan"),) * 2
+    res["label_upd"] = {"count": int(lab.sum()), "panels": int(nb[lab].sum()), "exec_us_per_panel_fit": float(per_panel),
+                        "exec_us_fixed_fit": float(ovh), "exec_us_sum_per_panel": float(ex[lab].sum() / nb[lab].sum()),
+                        "chip_ms": round(float(ex[lab].sum() / P / 1e3), 3),
+                        "by_nb": {int(b): round(float(ex[lab & (nb == b)].mean()), 2) for b in sorted(set(nb[lab]))}}
+    res["label_upd"]["paired_panels"] = int(nb[(typ == 5) & (tasks[:, 1] + 1 == nc)].sum())
+    full = (typ == 2) & (tasks[:, 1] < nc) & (tasks[:, 1] != tasks[:, 2])
+    if len(set(nb[full])) > 1:
+        res["full_upd_us_per_panel_fit"] = float(np.polyfit(nb[full].astype(float), ex[full], 1)[0])
 res["upd_panels"] = int(nb[typ == 2].sum())
 res["upd2_panels"] = int(nb[typ == 5].sum())  # (each covers two tiles)
 # DIAGX chain
