@@ -16,7 +16,7 @@ HDRS     := $(wildcard gpr_amd/csrc/*.h) include/gprx.h
 HOST_SRCS := $(wildcard gpr_amd/host/*.cpp)
 HOST_HDRS := $(wildcard include/gpr/*.h) include/gprx.h
 CXXFLAGS  ?= -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude
-CPPTESTS  := $(LIBDIR)/gp_host_test $(LIBDIR)/host_cpu_test $(LIBDIR)/gp_append_test
+CPPTESTS  := $(LIBDIR)/gp_host_test $(LIBDIR)/host_cpu_test $(LIBDIR)/gp_append_test $(LIBDIR)/pt_sched_test
 
 all: $(LIBDIR)/libgprx.so $(LIBDIR)/libgpr_amd.so cpptests oracle
 
@@ -44,6 +44,21 @@ cpptests: $(CPPTESTS)
 $(LIBDIR)/%: tests/cpp/%.cpp $(HOST_HDRS) $(LIBDIR)/libgpr_amd.so
 	$(CXX) $(CXXFLAGS) -o $@ $< -L$(LIBDIR) -lgpr_amd -lgprx -Wl,-rpath,'$$ORIGIN'
 
+# The schedule planner alone (host C++: no libgprx, no HIP runtime) under its stand-alone test
+# program; `make pt_sched_asan` builds the same two sources with the address and undefined-
+# behaviour sanitizers and runs the program (a CPU check: not part of `all`)
+PT_SCHED_SRCS  := tests/cpp/pt_sched_test.cpp gpr_amd/csrc/pt_sched.cpp
+PT_SCHED_HDRS  := gpr_amd/csrc/pt_sched.h gpr_amd/csrc/gprx_error.h include/gprx.h
+PT_SCHED_FLAGS := -O2 -g -std=c++17 -Wall -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include
+
+$(LIBDIR)/pt_sched_test: $(PT_SCHED_SRCS) $(PT_SCHED_HDRS) | $(LIBDIR)
+	$(CXX) $(PT_SCHED_FLAGS) -o $@ $(PT_SCHED_SRCS)
+
+pt_sched_asan: $(PT_SCHED_SRCS) $(PT_SCHED_HDRS) | $(BUILD)
+	$(CXX) $(PT_SCHED_FLAGS) -fsanitize=address,undefined -fno-sanitize-recover=all -fno-omit-frame-pointer \
+		-o $(BUILD)/pt_sched_test_asan $(PT_SCHED_SRCS)
+	$(BUILD)/pt_sched_test_asan
+
 oracle:
 	$(MAKE) -s -C oracle
 
@@ -54,4 +69,4 @@ clean:
 	rm -rf $(BUILD) $(LIBDIR)/*.so $(CPPTESTS)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean cpptests
+.PHONY: all oracle clean cpptests pt_sched_asan

@@ -9,6 +9,7 @@
 
 #include "../../include/gprx_dev.h"
 #include "gprx_internal.h"
+#include "pt_sched.h"
 
 namespace gprx {
 template <typename T>
@@ -339,10 +340,10 @@ extern "C" gprx_status gprx_dev_schedule(int32_t nc, int32_t nr, int32_t P, int3
         // build: bit 0 = fused covariance build, bit 1 = the last nc row blocks are identity,
         // bits 8..15 = chunk rule ratio + 1 (0: the one the simulation picks), bits 16..23 =
         // paired updates' row offset + 1 (0: the simulation's choice, 1: none), bit 2 = the narrow
-        // label row (row block nc, the only label block, leaves the pairs)
+        // label row (row block nc, the only label block, leaves the pairs), bit 3 = the f32 schedule
         const int64_t n = potrf_tiles_schedule_stats(nc, nr, P, (build & 1) != 0, est_us, (build & 2) ? nc : 0,
                                                      ((build >> 8) & 0xff) - 1, nullptr, 0, ((build >> 16) & 0xff) - 1,
-                                                     (build & 4) != 0);
+                                                     (build & 4) != 0, (build & 8) == 0);
         if (ntasks) *ntasks = n;
         return GPRX_OK;
     } catch (const Error& e) {
@@ -356,7 +357,7 @@ extern "C" int64_t gprx_dev_schedule_list(int32_t nc, int32_t nr, int32_t P, int
     try {
         return potrf_tiles_schedule_stats(nc, nr, P, (build & 1) != 0, nullptr, (build & 2) ? nc : 0,
                                           ((build >> 8) & 0xff) - 1, out, max, ((build >> 16) & 0xff) - 1,
-                                          (build & 4) != 0);
+                                          (build & 4) != 0, (build & 8) == 0);
     } catch (const Error& e) {
         std::fprintf(stderr, "gprx_dev_schedule_list: %s\n", e.msg.c_str());
         return -1;
@@ -418,9 +419,9 @@ extern "C" gprx_status gprx_dev_dist_schedule(int32_t nc, int32_t P, int32_t g, 
                                               double* est_us, int32_t* chunk_w, int64_t* ntasks) {
     if (nc < 1 || P < 1 || g < 1 || g > 32 || gb < 1 || ww < 1 || !est_us) return GPRX_ERR_ARG;
     try {
-        // flags bits 8..15: the update-chunk rule's ratio + 1 (0: the fixed rule)
+        // flags bits 8..15: the update-chunk rule's ratio + 1 (0: the fixed rule), bit 3: the f32 schedule
         const DistSched S = potrf_dist_schedule(nc, g, gb, ww, P, (flags & 1) != 0, (flags & 2) != 0,
-                                                std::max(0, ((flags >> 8) & 0xff) - 1));
+                                                std::max(0, ((flags >> 8) & 0xff) - 1), (flags & 8) == 0);
         *est_us = S.est_us;
         if (chunk_w) *chunk_w = S.W;
         if (ntasks) {
@@ -432,4 +433,20 @@ extern "C" gprx_status gprx_dev_dist_schedule(int32_t nc, int32_t P, int32_t g, 
         return GPRX_ERR_ARG;
     }
     return GPRX_OK;
+}
+
+extern "C" int64_t gprx_dev_dist_schedule_list(int32_t nc, int32_t P, int32_t g, int32_t gb, int32_t ww, int32_t flags,
+                                               int32_t rank, int32_t* out, int64_t max) {
+    if (nc < 1 || P < 1 || g < 1 || g > 32 || gb < 1 || ww < 1 || rank < 0 || rank >= g) return -1;
+    try {
+        const DistSched S = potrf_dist_schedule(nc, g, gb, ww, P, (flags & 1) != 0, (flags & 2) != 0,
+                                                std::max(0, ((flags >> 8) & 0xff) - 1), (flags & 8) == 0);
+        const std::vector<int4>& l = S.lists[rank];
+        if (out)
+            for (int64_t q = 0; q < (int64_t)l.size() && q < max; q++)
+                out[4 * q] = l[q].x, out[4 * q + 1] = l[q].y, out[4 * q + 2] = l[q].z, out[4 * q + 3] = l[q].w;
+        return (int64_t)l.size();
+    } catch (...) {
+        return -1;
+    }
 }

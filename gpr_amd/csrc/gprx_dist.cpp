@@ -50,6 +50,7 @@
 #include <vector>
 
 #include "gprx_dist.h"
+#include "pt_sched.h"
 
 namespace gprx {
 
@@ -578,7 +579,7 @@ static void setup(DistEngine<T>& E, const DistContext& C, int64_t n, int m, bool
         ww = pick;
         E.S = std::move(ps);
     }
-    // the update-chunk rule (k_ptiles.hip tile_chunks): the capped rules, tried for the chosen
+    // the update-chunk rule (pt_sched.cpp tile_chunks): the capped rules, tried for the chosen
     // grouping and window, replace the fixed one when they simulate > 0.5% shorter
     // (on every tile, or on the last 16 column blocks only: the chain-bound tail)
     for (int ratio : {4, 2})

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/gprx.h"
+#include "gprx_error.h"
 
 namespace gprx {
 
@@ -221,13 +222,8 @@ __device__ inline void gsincos(double x, double* s, double* c) { sincos(x, s, c)
 __device__ inline void gsincos(float x, float* s, float* c) { sincosf(x, s, c); }
 
 // ---------------------------------------------------------------------------------
-// Error helpers (host)
+// Error helpers (host): Error and GPRX_REQUIRE come from gprx_error.h
 // ---------------------------------------------------------------------------------
-struct Error {
-    gprx_status st;
-    std::string msg;
-};
-
 #define GPRX_HIP(call)                                                                             \
     do {                                                                                           \
         hipError_t e_ = (call);                                                                    \
@@ -235,12 +231,6 @@ struct Error {
             throw ::gprx::Error{e_ == hipErrorOutOfMemory ? GPRX_ERR_OOM : GPRX_ERR_HIP,           \
                                 std::string(#call) + ": " + hipGetErrorString(e_)};                \
     } while (0)
-
-#define GPRX_REQUIRE(cond, status, msg)                                                            \
-    do {                                                                                           \
-        if (!(cond)) throw ::gprx::Error{status, msg};                                             \
-    } while (0)
-
 
 // ---------------------------------------------------------------------------------
 // Opt-in per-kernel device timing (gprx_ctx_set_stats): HIP events around every launch
@@ -435,7 +425,7 @@ struct TileBuild {
 // Per diagonal block k, TP_STRIDE state words of the split diagonal step (k_ptiles.hip): [0..7]
 // TPART(k, p)'s phase, [TP_DPAN] DIAGX(k)'s published panels (the progressive TPART(k + 1, .)
 // follow it)
-constexpr int TP_STRIDE = 16, TP_DPAN = 8;  // (up to eight parts: k_ptiles.hip tp_parts)
+constexpr int TP_STRIDE = 16, TP_DPAN = 8;  // (up to eight parts: pt_sched.h tp_parts)
 
 // Distributed tile factorisation (k_ptiles.hip, potrf_tiles_kernel<T, true>; gprx_dist.cpp):
 // this rank's view of a factorisation whose row blocks are dealt over g ranks in groups of gb
@@ -509,20 +499,7 @@ struct DistLaunch {
     T* pbuf;           // [4][DB x DB] the TPART products
     int* tflag;        // [nc][TP_STRIDE] split-step states (zeroed per fit with the counters)
 };
-// The simulated schedule of a distributed factorisation: per-rank ticket lists (in start
-// order of one list-schedule simulation of all ranks, window flow control included), the
-// window-reading chunks per (rank, panel), and the predicted makespan.  ni > 0: nc identity
-// row blocks ride along (U = L^{-T}) plus the lower C = U U^T tiles (LML mode).
-struct DistSched {
-    std::vector<std::vector<int4>> lists;
-    std::vector<int> need;            // [g * nc]
-    std::vector<unsigned char> cons;  // [g * nr]: rank q reads row block j through its window
-    double est_us = 0;
-    int W = 0;              // update chunk width used
-};
-DistSched potrf_dist_schedule(int nc, int g, int gb, int ww, int P, bool build, bool inv, int ratio = 0, bool f64 = true,
-                              int tail = 0);
-bool potrf_split_for(bool f64, int P);  // the split diagonal step is on (this precision, P workgroups)
+// (the schedule the lists come from: pt_sched.h DistSched, potrf_dist_schedule, potrf_split_for)
 // GPRX_PT_DEBUG: the per-workgroup status words gprx_dev_pt_debug reads (k_ptiles.hip);
 // n = 0 unregisters dbg (if registered)
 void pt_debug_register(int* dbg, int n);
@@ -588,9 +565,6 @@ void launch_gemm_nt_kskip(T* C, int64_t ldc, const T* A, int64_t lda, const T* B
 template <typename T>
 void potrf_auto(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info, Exec& ex);
 bool potrf_uses_tiles();
-int64_t potrf_tiles_schedule_stats(int nc, int nr, int P, bool build, double* est_us, int ni = 0, int ratio = -1,
-                                   int32_t* list_out = nullptr, int64_t list_max = 0, int pair = -1,
-                                   bool narrow = false);
 // Generic C = beta C + alpha A B^T on GT-multiples (column-major).  lower: only tiles
 // with col-tile <= row-tile are computed, and inside diagonal tiles only row >= col.
 template <typename T>

@@ -14,6 +14,7 @@
 #pragma once
 #include "gprx_internal.h"
 #include "k_handoff.h"
+#include "pt_sched.h"  // the task types T_DIAGX .. T_UPD2 (shared with the host planner)
 
 namespace gprx {
 namespace mm {
@@ -21,9 +22,6 @@ namespace mm {
 constexpr int NT = 512;     // threads per workgroup
 constexpr int PAD = 16;     // LDS row pad (elements)
 
-// T_UPD2 (round 6): the update of two vertically adjacent tiles (i, j), (i + 1, j) over the same
-// panels as one 256 x 128 product (tile_mma_tall): the single-GPU factorisation's paired chunks
-enum { T_DIAGX = 0, T_TRSM = 1, T_UPD = 2, T_BUILD = 3, T_TPART = 4, T_UPD2 = 5 };
 enum { C_TICKET = 0, C_ERR = 1, C_NCTL = 16 };  // control words at the head of the counter block
 
 typedef double d4_t __attribute__((ext_vector_type(4)));

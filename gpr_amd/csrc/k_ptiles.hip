@@ -22,7 +22,7 @@
 //   DIAGX(k):  ver[k][k-1] == k-1, ver[k][k] == k-1, lcnt[k-1] >= k
 //   TRSM(i,k): ver[i][k] == k, lcnt[k] >= k+1
 //   UPD:       ver[i][j] == b0, lcnt[i] >= b0+nb, lcnt[j] >= b0+nb
-// The ticket order is a list schedule computed on the host (critical-path priorities,
+// The ticket order is a list schedule computed on the host (pt_sched.cpp: critical-path priorities,
 // simulated on P workers): every task's producers hold earlier tickets, and a workgroup that
 // holds a ticket is running, so the smallest unfinished ticket can always proceed -- no
 // deadlock whatever the real durations.  Every wait is also bounded in wall-clock time: a
@@ -41,15 +41,13 @@
 #include "gprx_internal.h"
 #include "k_handoff.h"
 #include "k_pairs.h"
+#include "pt_sched.h"
 
 #include <algorithm>
-#include <climits>
 #include <cstring>
 #include <cstdlib>
-#include <functional>
 #include <map>
 #include <mutex>
-#include <queue>
 #include <tuple>
 
 namespace gprx {
@@ -1235,35 +1233,6 @@ __device__ __forceinline__ void diag_factor_la(T* __restrict__ A, int64_t ld, T*
     }
 }
 
-// GPRX_TP_PROG (A/B builds): the progressive parts (tpart_prog) and DIAGX's panel counter.  Off
-// by default: same-box A/Bs (profiles/r04c_*, r04d_*) measured the chain step unchanged (C2
-// 1829 us against 1815 for the Linv form without the panel counter; the counter's stores and
-// drains cost DIAGX ~1.3 us per step, the early X_3 saves ~2 us of the parts' T phase, and the
-// parts' S phase, not T, dominates after DIAGX(k-1) ends) and C3 0.1-0.4% slower.
-#ifdef GPRX_TP_PROG
-__host__ __device__ constexpr bool tp_linv_form() { return false; }
-#else
-__host__ __device__ constexpr bool tp_linv_form() { return true; }
-#endif
-// TPART workgroups per split diagonal step: f64 (the Linv form) eight -- part p = C + 4 h takes
-// the column groups C, 7 - C of T's rows 64 h .. 64 h + 63 and the S quarter of tile-rows C, 7 - C
-// over T's columns 64 h .. 64 h + 63 (tpart_run8) -- f32 and the progressive form four
-// (GPRX_TP_PARTS4: four for f64 too)
-#ifdef GPRX_TP_PARTS4
-__host__ __device__ constexpr int tp_parts(bool f64) { return (void)f64, 4; }
-#else
-__host__ __device__ constexpr int tp_parts(bool f64) { return f64 && tp_linv_form() ? 8 : 4; }
-#endif
-#ifdef GPRX_NO_SPLIT  // (A/B builds: the split diagonal step compiled out)
-constexpr bool SPLIT_CODE = false;
-#else
-constexpr bool SPLIT_CODE = true;
-#endif
-#ifndef GPRX_DIAG_RANK8
-constexpr bool DIAG_LA = true;
-#else
-constexpr bool DIAG_LA = false;
-#endif
 // from_lds (f64 look-ahead form only): the block is in the LDS image already (diagx_ts)
 // (out of line: its registers (fact32's accumulators, the pivot block) no longer count against
 // the task loop, which sits at 256 VGPRs -- inlined, any growth of the loop spilled, and a
@@ -2660,755 +2629,6 @@ __global__ __launch_bounds__(NT) void potrf_tiles_kernel(Args<T> a) {
     if (wv == 0 && ld_agent(a.ctl + C_ERR)) atomicMin(a.info, -1);
 }
 
-// ==========================================================================================
-// Host: task list + list-schedule simulation
-// ==========================================================================================
-struct Cost {  // per-task durations (us, one CU), calibrated from GPRX_PT_TRACE timelines
-    double k128 = 17.1;  // per 128-deep slice of a full tile update
-    double ovh = 6.5;    // per update task: ticket, waits, fences, C read-modify-write
-    double trsm = 16.0;  // TRSM tile (r01i trace: 15.9)
-    double diagx = 70.0;   // DIAGX(k > 0): trsm + syrk tile + 128x128 factor/inverse (r02f trace, f64)
-    double diag0 = 40.0;   // DIAGX(0): factor/inverse only
-    double early = 31.0;   // DIAGX(k) publishes L_{k,k-1} after its trsm and syrk phases
-    double diagf = 0.97;   // diagonal-tile update relative to a full one (2 of 8 waves idle)
-    double build = 28.0;   // BUILD tile (pair statistics + kernel values + stores)
-    // the split diagonal step (f64): TPART(k, c) takes tpart + tpart_c (c + 1); DIAGX(k) then
-    // sums the products and factors (diagx_s), publishing L_{k,k-1} early_s into it
-    // (r03w trace, N = 4096: the parts publish S ~12 us after Linv_{k-1}, DIAGX copies it in
-    // 2 us and factors; step 54.4 us)
-    double tpart = 11.5, tpart_c = 0.0;
-    double diagx_s = 44.0, early_s = 2.0;
-    // the progressive parts (f64, tpart_prog; DIAGX(k-1) on the same rank): they follow DIAGX(k-1)'s
-    // panels and publish S this long after its end (X_3, T and S remain after its last fact32,
-    // ~8 us before its end)
-    double tpart_prog = 2.5;
-    bool prog = false;  // this schedule is for the progressive form (set by the callers)
-    int np = 4;         // TPART tasks per split step (tp_parts; set by the callers)
-    // a paired update (T_UPD2) per panel, relative to two single-tile panels (the 256 x 128
-    // mainloop's probe rate against the 128 x 128 tile's: 0.877 / 0.901)
-    double tall = 0.975;
-    // which chunks pair (make_schedule pair > 0): at least pair_nbmin panels wide, in the columns
-    // before the last pair_tail (GPRX_PT_PAIR_NBMIN / GPRX_PT_PAIR_TAIL)
-    int pair_nbmin = 1, pair_tail = 0;
-    // per 128-deep slice of a narrow label-row update (make_schedule narrow; GPRX_PT_KLAB_US);
-    // < 0: priced as a full tile's (k128).  C3 fit traces: 4.3-4.5 us per panel against 15.7 for a
-    // full tile (profiles/label_rows_pt_trace_fit16384_narrow*.json); priced so, C3's launch
-    // 24.28-24.30 -> 24.22-24.23 ms, same box, three rounds (profiles/label_rows_ab.txt)
-    double klab = 4.3;
-};
-
-// TPART tickets of one k in the order TPART(k, np-1), .., (k, 0): each part waits for
-// the reads of the parts with a larger c, so those must hold the earlier tickets (the parts
-// have the same inputs and one consumer, DIAGX(k): permuting them over their slots keeps
-// every other order of the list)
-static void order_tparts(std::vector<int4>& list) {
-    std::map<int, std::vector<int>> pos;
-    for (size_t q = 0; q < list.size(); q++)
-        if ((list[q].x & 0xff) == T_TPART) pos[list[q].y].push_back((int)q);
-    for (auto& kv : pos) {
-        std::vector<int>& v = kv.second;
-        std::sort(v.begin(), v.end());
-        for (size_t u = 0; u < v.size(); u++) list[v[u]].z = (int)v.size() - 1 - (int)u;
-    }
-}
-
-struct Task {
-    int type, i, j, b0, nb;
-    double dur;
-    std::vector<int> succ, esucc;  // esucc: released at the early publication (DIAGX)
-    int ndep = 0;
-    double bl = 0;  // bottom level (longest path to the end, inclusive)
-};
-
-struct Schedule {
-    std::vector<int4> list;
-    double est_us = 0;
-    int64_t ntasks = 0;
-    // identity rows paired (make_schedule): an odd identity row block 2s + 1 starts its updates at
-    // panel 2s with its partner -- its counters start there and its tile at column 2s is zeroed
-    bool ident_even = false;
-};
-
-// Chunks of the updates of tile (i, j): b in [0, e), e = j (i > j) or j - 1 (diagonal tile:
-// the last one is applied inside DIAGX(j)).  Aligned W-chunks up to the last multiple of W
-// at or before column j, then the remainder before the last `near` panels in power-of-two
-// pieces (W/2, W/4, ..., 1), then single panels -- few tasks (each costs a fixed ~6 us of
-// ticket, waits, fences and C read-modify-write), while the last panels of a tile, the ones
-// the diagonal chain waits for, still go one at a time.
-// s > 0 (an identity row block of the inverse, whose panels before s are zero): the same
-// rule on the panels [s, e), shifted.
-// ratio > 0 (chosen per shape by the simulated makespan, potrf_tiles): greedy from the first
-// panel, the widest power-of-two piece p <= W (W-aligned when p == W) that ends at least `near`
-// panels before e and is at most ratio x the panels left after it.  A piece can start only
-// when its last panel is final, so a wide piece close to the tile's last panel holds up the
-// tile's consumer: at N = 4096 the [0, 16) piece of tiles (18, 17) and (18, 18) became ready
-// with panel 15 and ran 280 us, and DIAGX(18) waited 184 us for it (r03 trace).
-static void tile_chunks(int i, int j, int W, int near, std::vector<std::pair<int, int>>& out, int s = 0,
-                        int ratio = 0) {
-    out.clear();
-    const int e = ((i == j) ? j - 1 : j) - s;
-    if (e <= 0) return;
-    if (ratio > 0) {
-        for (int b = 0; b < e;) {
-            int p = W;
-            for (; p > 1; p /= 2) {
-                if (p == W && b % W) continue;
-                const int end = b + p;
-                if (end > e - near || p > ratio * (e - end)) continue;
-                break;
-            }
-            out.push_back({s + b, p});
-            b += p;
-        }
-        return;
-    }
-    int hb = std::max(0, std::min(W * ((j - s) / W), e));
-    hb -= hb % W;
-    int b = 0;
-    for (; b + W <= hb; b += W) out.push_back({s + b, W});
-    for (int p = W / 2; p >= 1; p /= 2)
-        if (b + p <= e - near) {
-            out.push_back({s + b, p});
-            b += p;
-        }
-    for (; b < e; b++) out.push_back({s + b, 1});
-}
-
-// ni > 0: the last ni row blocks are the identity (the inverse L^{-1} riding along as
-// L^{-T} rows): identity block a = i - (nr - ni) has zero L blocks before column block a.
-// tail > 0: the capped rule (ratio) only for the tiles of the last `tail` column blocks, the
-// fixed rule before them
-// pair > 0 (round 6): the off-diagonal tiles of column j from row j + pair down to the last label
-// row go in vertical pairs (j + pair, j + pair + 1), ..., each pair's identical chunks as ONE
-// T_UPD2 task (a 256 x 128 update: tile_gemm_tall); the `pair` - 1 tiles right below the
-// diagonal -- the diagonal chain's inputs -- and the identity rows stay single
-// narrow: the label row block nc (the only one) updates as a 16-row product (tile_gemm_rows16).  As
-// the bottom of a pair it would gain nothing -- the pair lasts as long as the waves that hold the
-// matrix row -- so it is never one: the rows i >= nc leave the pairs, row nc - 1 runs single in
-// the columns where it was the label row's top, and the label updates are priced at Cost::klab
-static Schedule make_schedule(int nc, int nr, int W, int near, int P, const Cost& cm0, bool build, int ni = 0,
-                              int ratio = 0, bool split = false, int tail = 0, int pair = 0, bool narrow = false) {
-    Cost cm = cm0;
-    if (split) cm.early = cm.early_s;
-    const int nr0 = nr - ni;
-    narrow = narrow && nr0 == nc + 1;
-    const int pend = narrow ? nc : nr0;  // the matrix-row pairs end before row block pend
-    auto start_of = [&](int i) { return i >= nr0 ? i - nr0 : 0; };
-    // identity rows in pairs (E_2s, E_2s+1): both update from panel 2s -- the bottom row's block at
-    // column 2s is a stored zero (potrf_tiles zeroes it and starts its counters at 2s), so its
-    // one extra panel subtracts nothing and the two rows' chunk lists are identical
-    static const bool id_pair = [] {
-        const char* e = std::getenv("GPRX_PT_IDPAIR");  // 0: identity rows single (A/B)
-        return !(e && std::atoi(e) == 0);
-    }();
-    const bool ident_even = id_pair && pair > 0 && ni > 1;
-    // identity pairs in the last pair_tail columns too (the tail rule spares the factor's
-    // chain-bound last columns; the identity rows' updates there are bulk work): LML N = 8192
-    // 73.66 -> 73.05 ms with both (profiles/r06z_idpair_ab.txt); GPRX_PT_IDTAIL=0 restricts them
-    static const bool id_tail = [] {
-        const char* e = std::getenv("GPRX_PT_IDTAIL");
-        return !(e && std::atoi(e) == 0);
-    }();
-    auto cstart = [&](int i) {
-        const int a = start_of(i);
-        return (ident_even && i >= nr0) ? a - (a & 1) : a;
-    };
-    // row i of column j: 1 the top of a pair, 2 its bottom, 0 single
-    auto pair_role = [&](int i, int j) {
-        if (pair <= 0) return 0;
-        if (i >= nr0) {  // identity rows: (E_2s, E_2s+1)
-            const int a = i - nr0;
-            if (!ident_even) return 0;
-            if ((a & 1) == 0) return a + 1 < ni ? 1 : 0;
-            return 2;
-        }
-        const int r0 = j + pair;
-        if (i >= r0 && (i - r0) % 2 == 0 && i + 1 < pend) return 1;
-        if (i - 1 >= r0 && (i - 1 - r0) % 2 == 0 && i < pend) return 2;
-        return 0;
-    };
-    std::vector<Task> tasks;
-    tasks.reserve((size_t)nr * nc * 2);
-    auto add = [&](int type, int i, int j, int b0, int nb, double dur) {
-        Task tk;
-        tk.type = type;
-        tk.i = i;
-        tk.j = j;
-        tk.b0 = b0;
-        tk.nb = nb;
-        tk.dur = dur;
-        tasks.push_back(std::move(tk));
-        return (int)tasks.size() - 1;
-    };
-    std::vector<int> diagx(nc, -1);
-    std::vector<int> trsm((size_t)nr * nc, -1);
-    std::vector<int> last_upd((size_t)nr * nc, -1);
-    std::vector<std::vector<int>> deps, edeps;  // edeps: on L_{k,k-1}, published early by DIAGX(k)
-    auto dep = [&](int tsk, int on, bool early = false) {
-        if (on < 0) return;
-        auto& d = early ? edeps : deps;
-        if ((int)d.size() <= tsk) d.resize(tsk + 1);
-        d[tsk].push_back(on);
-    };
-    // producer of L_{i,b} (early: the trsm phase of DIAGX(i) already published it)
-    auto prodL = [&](int i, int b, bool& early) -> int {
-        early = i < nc && b == i - 1;
-        if (i < nc && (b == i || b == i - 1)) return diagx[i];
-        return trsm[(size_t)i * nc + b];
-    };
-    // update chunks bucketed by their last block
-    struct Chunk {
-        int i, j, b0, nb;
-    };
-    std::vector<std::vector<Chunk>> by_last(nc);
-    {
-        std::vector<std::pair<int, int>> ch;
-        for (int j = 1; j < nc; j++)
-            for (int i = j; i < nr; i++) {
-                tile_chunks(i, j, W, near, ch, cstart(i), (tail <= 0 || j >= nc - tail) ? ratio : 0);
-                for (auto& c : ch) by_last[c.first + c.second - 1].push_back(Chunk{i, j, c.first, c.second});
-            }
-    }
-    auto make_diagx = [&](int k) {
-        if (split && k >= 1) {  // TPART(k, np-1..0), then DIAGX(k) on their products
-            int tp[8];
-            for (int c = cm.np - 1; c >= 0; c--) {
-                tp[c] = add(T_TPART, k, c, 0, 0, cm.prog ? cm.tpart_prog : cm.tpart + cm.tpart_c * (c + 1));
-                dep(tp[c], diagx[k - 1]);
-                dep(tp[c], last_upd[(size_t)k * nc + (k - 1)]);
-                dep(tp[c], last_upd[(size_t)k * nc + k]);  // phase 2 starts from A_kk
-            }
-            const int id = add(T_DIAGX, k, k, 0, 0, cm.diagx_s);
-            diagx[k] = id;
-            for (int c = 0; c < cm.np; c++) dep(id, tp[c]);
-            dep(id, last_upd[(size_t)k * nc + k]);
-            return;
-        }
-        const double dur = (k == 0) ? cm.diag0 : cm.diagx;
-        const int id = add(T_DIAGX, k, k, 0, 0, dur);
-        diagx[k] = id;
-        if (k >= 1) {
-            dep(id, diagx[k - 1]);
-            dep(id, last_upd[(size_t)k * nc + (k - 1)]);
-            dep(id, last_upd[(size_t)k * nc + k]);
-        }
-    };
-    // Creation order (checked below) puts every producer before its consumers:
-    // [BUILD(i, j) for the lower tiles], DIAGX(0); per k: TRSM(., k), DIAGX(k+1), the update
-    // chunks ending at block k.  A tile's BUILD is its first "update".
-    if (build)
-        for (int i = 0; i < nc; i++)
-            for (int j = 0; j <= i; j++) last_upd[(size_t)i * nc + j] = add(T_BUILD, i, j, 0, 0, cm.build);
-    make_diagx(0);
-    dep(diagx[0], last_upd[0]);
-    for (int k = 0; k < nc; k++) {
-        for (int i = k + 1; i < nr; i++) {
-            if (i == k + 1 && i < nc) continue;  // inside DIAGX(k+1)
-            if (k < start_of(i)) continue;        // zero block of an identity row
-            const int id = add(T_TRSM, i, k, 0, 0, cm.trsm);
-            trsm[(size_t)i * nc + k] = id;
-            dep(id, diagx[k]);
-            dep(id, last_upd[(size_t)i * nc + k]);
-        }
-        if (k + 1 < nc) make_diagx(k + 1);
-        for (const Chunk& c : by_last[k]) {
-            const bool pairable = c.nb >= cm.pair_nbmin && (c.j < nc - cm.pair_tail || (c.i >= nr0 && id_tail));
-            const int role = pairable ? pair_role(c.i, c.j) : 0;
-            if (role == 2) continue;  // (the pair's top row made the task: identical chunks)
-            if (role == 1) {
-                const int id = add(T_UPD2, c.i, c.j, c.b0, c.nb, cm.ovh + 2.0 * c.nb * cm.k128 * cm.tall);
-                bool e1, e2, e3;
-                for (int r = c.i; r <= c.i + 1; r++) dep(id, last_upd[(size_t)r * nc + c.j]);
-                const int p1 = prodL(c.i, k, e1), p3 = prodL(c.i + 1, k, e3), p2 = prodL(c.j, k, e2);
-                dep(id, p1, e1);
-                dep(id, p3, e3);
-                dep(id, p2, e2);
-                last_upd[(size_t)c.i * nc + c.j] = id;
-                last_upd[(size_t)(c.i + 1) * nc + c.j] = id;
-                continue;
-            }
-            const bool lab = narrow && c.i == nc && cm.klab >= 0;
-            const double dur = cm.ovh + c.nb * (lab ? cm.klab : cm.k128 * (c.i == c.j ? cm.diagf : 1.0));
-            const int id = add(T_UPD, c.i, c.j, c.b0, c.nb, dur);
-            dep(id, last_upd[(size_t)c.i * nc + c.j]);
-            bool e1, e2;
-            const int p1 = prodL(c.i, k, e1), p2 = prodL(c.j, k, e2);
-            dep(id, p1, e1);
-            dep(id, p2, e2);
-            last_upd[(size_t)c.i * nc + c.j] = id;
-        }
-    }
-    const int nt = (int)tasks.size();
-    deps.resize(nt);
-    edeps.resize(nt);
-    for (int id = 0; id < nt; id++) {
-        auto& d = deps[id];
-        auto& ed = edeps[id];
-        std::sort(d.begin(), d.end());
-        d.erase(std::unique(d.begin(), d.end()), d.end());
-        std::sort(ed.begin(), ed.end());
-        ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
-        for (int on : d) {
-            if (on >= id) throw Error{GPRX_ERR_ARG, "potrf tile schedule: producer created after consumer"};
-            tasks[on].succ.push_back(id);
-        }
-        int ne = 0;
-        for (int on : ed) {
-            if (on >= id) throw Error{GPRX_ERR_ARG, "potrf tile schedule: producer created after consumer"};
-            if (std::binary_search(d.begin(), d.end(), on)) continue;  // full dependency already
-            tasks[on].esucc.push_back(id);
-            ne++;
-        }
-        tasks[id].ndep = (int)d.size() + ne;
-    }
-    // creation order is topological: bottom levels in reverse
-    for (int id = nt - 1; id >= 0; id--) {
-        double m = 0;
-        for (int s : tasks[id].succ) m = std::max(m, tasks[s].bl);
-        for (int s : tasks[id].esucc) m = std::max(m, tasks[s].bl - (tasks[id].dur - cm.early));
-        tasks[id].bl = tasks[id].dur + m;
-    }
-    // list scheduling on P workers, highest bottom level first
-    typedef std::pair<double, int> PQ;
-    std::priority_queue<PQ> ready;
-    // events: (time, task) finishing, or (time, -1 - task) for an early publication
-    std::priority_queue<PQ, std::vector<PQ>, std::greater<PQ>> running;
-    std::vector<int> indeg(nt);
-    for (int id = 0; id < nt; id++) {
-        indeg[id] = tasks[id].ndep;
-        if (indeg[id] == 0) ready.push({tasks[id].bl, id});
-    }
-    Schedule S;
-    S.list.reserve(nt);
-    double now = 0;
-    int freew = P;
-    while ((int)S.list.size() < nt || !running.empty()) {
-        while (freew > 0 && !ready.empty()) {
-            const int id = ready.top().second;
-            ready.pop();
-            const Task& tk = tasks[id];
-            S.list.push_back(make_int4(tk.type | (tk.nb << 8), tk.i, tk.j, tk.b0));
-            running.push({now + tk.dur, id});
-            if (!tk.esucc.empty()) running.push({now + std::min(cm.early, tk.dur), -1 - id});
-            freew--;
-        }
-        if (running.empty()) throw Error{GPRX_ERR_ARG, "potrf tile schedule: dependency cycle"};
-        const PQ f = running.top();
-        running.pop();
-        now = f.first;
-        if (f.second < 0) {
-            for (int s : tasks[-1 - f.second].esucc)
-                if (--indeg[s] == 0) ready.push({tasks[s].bl, s});
-            continue;
-        }
-        freew++;
-        for (int s : tasks[f.second].succ)
-            if (--indeg[s] == 0) ready.push({tasks[s].bl, s});
-    }
-    S.est_us = now;
-    S.ntasks = nt;
-    S.ident_even = ident_even;
-    if (split) order_tparts(S.list);
-    return S;
-}
-
-// ------------------------------------------------------------------------------------------
-// Distributed schedule (gprx_dist.cpp): the single-GPU task DAG with row block i on rank
-// own(i) = (i / gb) mod g (identity row E_a with row a), plus, as timed nodes that occupy no
-// worker:
-//   push(i, b)   tile L_ib from its rank into the window of every rank that reads row i
-//   pushL(k)     Linv_k from DIAGX(k)'s rank into every other rank's Linv array
-//   rel(q, p)    rank q's last window-reading update chunk covering panel p is done: the window
-//                slot p mod ww may be refilled on q
-// A task whose input lives on another rank depends on its push node; a task that pushes a tile
-// of panel b into a window depends on rel(q, b - ww) of every consumer q (flow control: chunks
-// are at most ww / 2 panels wide, so a release never waits on the panel being pushed).
-// Simulated on g x P workers; each rank's ticket list is its tasks in start order.  The
-// simulation order is one topological order of the whole DAG, flow control included, so the
-// unfinished task that started first in the simulation always has its inputs and a worker:
-// the single-GPU deadlock argument, extended to the ranks and their windows.
-//
-// inv (LML mode): nc identity row blocks E_a = nc + 1 + a ride along (U = L^{-T}, tiles
-// (E_a, b), b >= a) and the lower C = U U^T accumulates in tiles (E_a, E_c), c <= a, as
-// update chunks over the panels b >= a (C_ac = -sum_b U_ab U_cb^T, stored negated).
-// ------------------------------------------------------------------------------------------
-static void c_chunks(int a, int W, int nc, std::vector<std::pair<int, int>>& out) {
-    out.clear();
-    for (int b = a; b < nc;) {
-        const int e = std::min(nc, (b / W + 1) * W);
-        out.push_back({b, e - b});
-        b = e;
-    }
-}
-
-static DistSched make_schedule_dist(int nc, bool inv, int W, int near, int P, int g, int gb, int ww, const Cost& cm0,
-                                    bool build, double push_us, double rel_us, int ratio = 0, bool split = false,
-                                    int tail = 0) {
-    Cost cm = cm0;
-    if (split) cm.early = cm.early_s;
-    const int nr = nc + 1 + (inv ? nc : 0), nci = inv ? 2 * nc : nc;
-    auto own = [&](int i) { return i <= nc ? (i / gb) % g : ((i - nc - 1) / gb) % g; };
-    auto colx = [&](int j) { return j > nc ? j - 1 : j; };  // counter column of tile (., j)
-    auto start_of = [&](int i) { return i > nc ? i - nc - 1 : 0; };
-    std::vector<Task> tasks;
-    std::vector<int> rank_of;  // -1: transport node
-    auto add = [&](int type, int i, int j, int b0, int nb, double dur, int rk) {
-        Task tk;
-        tk.type = type;
-        tk.i = i;
-        tk.j = j;
-        tk.b0 = b0;
-        tk.nb = nb;
-        tk.dur = dur;
-        tasks.push_back(std::move(tk));
-        rank_of.push_back(rk);
-        return (int)tasks.size() - 1;
-    };
-    std::vector<int> diagx(nc, -1), pushl(nc, -1);
-    std::vector<int> trsm((size_t)nr * nc, -1), push((size_t)nr * nc, -1), last_upd((size_t)nr * nci, -1);
-    std::vector<std::vector<int>> deps, edeps;
-    auto dep = [&](int tsk, int on, bool early = false) {
-        if (on < 0) return;
-        auto& d = early ? edeps : deps;
-        if ((int)d.size() <= tsk) d.resize(tsk + 1);
-        d[tsk].push_back(on);
-    };
-    auto prodL = [&](int i, int b, bool& early) -> int {
-        early = i < nc && b == i - 1;
-        if (i < nc && (b == i || b == i - 1)) return diagx[i];
-        return trsm[(size_t)i * nc + b];
-    };
-    auto linv = [&](int k, int rk) { return own(k) == rk ? diagx[k] : pushl[k]; };
-    // the update chunks: (i, j, b0, nb), bucketed by their last panel
-    struct Chunk {
-        int i, j, b0, nb;
-    };
-    std::vector<std::vector<Chunk>> by_last(nc);
-    {
-        std::vector<std::pair<int, int>> ch;
-        for (int j = 1; j < nc; j++)
-            for (int i = j; i < nr; i++) {
-                if (i > nc && start_of(i) >= j) continue;  // identity row E_a: tiles (E_a, j > a) only
-                tile_chunks(i, j, W, near, ch, start_of(i), (tail <= 0 || j >= nc - tail) ? ratio : 0);
-                for (auto& c : ch) by_last[c.first + c.second - 1].push_back(Chunk{i, j, c.first, c.second});
-            }
-        if (inv)
-            for (int aa = 0; aa < nc; aa++) {
-                c_chunks(aa, W, nc, ch);
-                for (int c = 0; c <= aa; c++)
-                    for (auto& x : ch) by_last[x.first + x.second - 1].push_back(Chunk{nc + 1 + aa, nc + 1 + c, x.first, x.second});
-            }
-    }
-    // who reads which row through the window, and the window-reading chunks per (rank, panel)
-    DistSched S;
-    S.cons.assign((size_t)g * nr, 0);
-    S.need.assign((size_t)g * nc, 0);
-    for (int k = 0; k < nc; k++)
-        for (const Chunk& c : by_last[k]) {
-            const int q = own(c.i);
-            if (own(c.j) == q) continue;
-            S.cons[(size_t)q * nr + c.j] = 1;
-            for (int p = c.b0; p < c.b0 + c.nb; p++) S.need[(size_t)q * nc + p]++;
-        }
-    std::vector<int> rel((size_t)g * nc, -1);
-    // producers of panel p's window tiles wait for every consumer's release of panel p - ww
-    auto flow = [&](int id, int i, int p) {
-        if (i == nc || p - ww < 0) return;  // the label rows go to the z area, not the window
-        for (int q = 0; q < g; q++)
-            if (q != own(i) && S.cons[(size_t)q * nr + i]) dep(id, rel[(size_t)q * nc + (p - ww)]);
-    };
-    auto make_push = [&](int i, int b, int prod) {
-        bool any = false;
-        for (int q = 0; q < g && !any; q++) any = q != own(i) && S.cons[(size_t)q * nr + i];
-        if (!any) return;
-        const int id = add(-2, i, b, 0, 0, push_us, -1);
-        push[(size_t)i * nc + b] = id;
-        dep(id, prod);
-    };
-    auto make_diagx = [&](int k) {
-        int tp[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-        if (split && k >= 1)  // TPART(k, np-1..0) on the owner of row block k
-            for (int c = cm.np - 1; c >= 0; c--) {
-                tp[c] = add(T_TPART, k, c, 0, 0,
-                            (cm.prog && own(k - 1) == own(k)) ? cm.tpart_prog : cm.tpart + cm.tpart_c * (c + 1), own(k));
-                dep(tp[c], linv(k - 1, own(k)));
-                dep(tp[c], last_upd[(size_t)k * nci + (k - 1)]);
-                dep(tp[c], last_upd[(size_t)k * nci + k]);  // phase 2 starts from A_kk
-            }
-        const int id = add(T_DIAGX, k, k, 0, 0, (k == 0) ? cm.diag0 : (split ? cm.diagx_s : cm.diagx), own(k));
-        diagx[k] = id;
-        if (k >= 1) {
-            for (int c = 0; c < cm.np; c++) dep(id, tp[c]);
-            dep(id, linv(k - 1, own(k)));
-            dep(id, last_upd[(size_t)k * nci + (k - 1)]);
-            dep(id, last_upd[(size_t)k * nci + k]);
-            flow(id, k, k - 1);  // it pushes L_{k,k-1} into window slot k - 1
-            make_push(k, k - 1, id);
-        }
-        pushl[k] = add(-3, k, k, 0, 0, push_us, -1);
-        dep(pushl[k], id);
-    };
-    if (build)
-        for (int i = 0; i < nc; i++)
-            for (int j = 0; j <= i; j++) last_upd[(size_t)i * nci + j] = add(T_BUILD, i, j, 0, 0, cm.build, own(i));
-    make_diagx(0);
-    dep(diagx[0], last_upd[0]);
-    for (int k = 0; k < nc; k++) {
-        if (k - ww >= 0)  // releases of panel k - ww: every chunk covering it was created already
-            for (int q = 0; q < g; q++) {
-                const int p = k - ww;
-                if (!S.need[(size_t)q * nc + p]) continue;
-                rel[(size_t)q * nc + p] = add(-4, q, p, 0, 0, rel_us, -1);  // its chunks: wired below
-            }
-        for (int i = k + 1; i < nr; i++) {
-            if (i == k + 1 && i < nc) continue;  // inside DIAGX(k+1)
-            if (k < start_of(i)) continue;        // zero block of an identity row
-            const int id = add(T_TRSM, i, k, 0, 0, cm.trsm, own(i));
-            trsm[(size_t)i * nc + k] = id;
-            dep(id, linv(k, own(i)));
-            dep(id, last_upd[(size_t)i * nci + k]);
-            flow(id, i, k);
-            make_push(i, k, id);
-        }
-        if (k + 1 < nc) make_diagx(k + 1);
-        for (const Chunk& c : by_last[k]) {
-            const int rk = own(c.i);
-            const double dur = cm.ovh + c.nb * cm.k128 * (c.i == c.j ? cm.diagf : 1.0);
-            const int id = add(T_UPD, c.i, c.j, c.b0, c.nb, dur, rk);
-            dep(id, last_upd[(size_t)c.i * nci + colx(c.j)]);
-            bool e1, e2;
-            dep(id, prodL(c.i, k, e1), e1);
-            if (own(c.j) == rk) {
-                dep(id, prodL(c.j, k, e2), e2);
-            } else {
-                for (int b = c.b0; b <= k; b++) dep(id, push[(size_t)c.j * nc + b]);
-            }
-            last_upd[(size_t)c.i * nci + colx(c.j)] = id;
-        }
-    }
-    // the release nodes depend on the chunks that read the window (chunks are at most W <= ww
-    // panels wide, so every chunk covering panel p was created before rel(., p))
-    const int nt = (int)tasks.size();
-    deps.resize(nt);
-    edeps.resize(nt);
-    for (int id = 0; id < nt; id++) {
-        if (rank_of[id] >= 0 && tasks[id].type == T_UPD) {
-            const Task& c = tasks[id];
-            const int q = rank_of[id];
-            if (own(c.j) != q)
-                for (int p = c.b0; p < c.b0 + c.nb; p++) {
-                    const int r = rel[(size_t)q * nc + p];
-                    if (r >= 0) deps[r].push_back(id);
-                }
-        }
-    }
-    for (int id = 0; id < nt; id++) {
-        auto& d = deps[id];
-        auto& ed = edeps[id];
-        std::sort(d.begin(), d.end());
-        d.erase(std::unique(d.begin(), d.end()), d.end());
-        std::sort(ed.begin(), ed.end());
-        ed.erase(std::unique(ed.begin(), ed.end()), ed.end());
-        for (int on : d) {
-            if (on >= id) throw Error{GPRX_ERR_ARG, "potrf dist schedule: producer created after consumer"};
-            tasks[on].succ.push_back(id);
-        }
-        int ne = 0;
-        for (int on : ed) {
-            if (on >= id) throw Error{GPRX_ERR_ARG, "potrf dist schedule: producer created after consumer"};
-            if (std::binary_search(d.begin(), d.end(), on)) continue;
-            tasks[on].esucc.push_back(id);
-            ne++;
-        }
-        tasks[id].ndep = (int)d.size() + ne;
-    }
-    // bottom levels: a release node's producers may come after it in id order, so iterate the
-    // longest-path recurrence to a fixed point over a topological order (Kahn)
-    {
-        std::vector<int> indeg(nt, 0), order;
-        order.reserve(nt);
-        for (int id = 0; id < nt; id++)
-            for (int s2 : tasks[id].succ) indeg[s2]++;
-        for (int id = 0; id < nt; id++)
-            for (int s2 : tasks[id].esucc) indeg[s2]++;
-        std::vector<int> st;
-        for (int id = 0; id < nt; id++)
-            if (!indeg[id]) st.push_back(id);
-        while (!st.empty()) {
-            const int id = st.back();
-            st.pop_back();
-            order.push_back(id);
-            for (int s2 : tasks[id].succ)
-                if (--indeg[s2] == 0) st.push_back(s2);
-            for (int s2 : tasks[id].esucc)
-                if (--indeg[s2] == 0) st.push_back(s2);
-        }
-        if ((int)order.size() != nt) throw Error{GPRX_ERR_ARG, "potrf dist schedule: dependency cycle"};
-        for (int x = nt - 1; x >= 0; x--) {
-            const int id = order[x];
-            double m = 0;
-            for (int s2 : tasks[id].succ) m = std::max(m, tasks[s2].bl);
-            for (int s2 : tasks[id].esucc) m = std::max(m, tasks[s2].bl - (tasks[id].dur - cm.early));
-            tasks[id].bl = tasks[id].dur + m;
-        }
-    }
-    typedef std::pair<double, int> PQ;
-    std::vector<std::priority_queue<PQ>> ready(g);
-    std::priority_queue<PQ, std::vector<PQ>, std::greater<PQ>> running;
-    std::vector<int> indeg(nt), freew(g, P);
-    S.lists.assign(g, {});
-    double now = 0;
-    int started = 0;
-    auto make_ready = [&](int id) {
-        if (rank_of[id] < 0) {  // transport / release: starts at once, no worker
-            running.push({now + tasks[id].dur, id});
-            started++;
-        } else {
-            ready[rank_of[id]].push({tasks[id].bl, id});
-        }
-    };
-    for (int id = 0; id < nt; id++) {
-        indeg[id] = tasks[id].ndep;
-        if (indeg[id] == 0) make_ready(id);
-    }
-    while (started < nt || !running.empty()) {
-        for (int rk = 0; rk < g; rk++)
-            while (freew[rk] > 0 && !ready[rk].empty()) {
-                const int id = ready[rk].top().second;
-                ready[rk].pop();
-                const Task& tk = tasks[id];
-                S.lists[rk].push_back(make_int4(tk.type | (tk.nb << 8), tk.i, tk.j, tk.b0));
-                running.push({now + tk.dur, id});
-                if (!tk.esucc.empty()) running.push({now + std::min(cm.early, tk.dur), -1 - id});
-                freew[rk]--;
-                started++;
-            }
-        if (running.empty()) throw Error{GPRX_ERR_ARG, "potrf dist schedule: dependency cycle"};
-        const PQ f = running.top();
-        running.pop();
-        now = f.first;
-        if (f.second < 0) {
-            for (int s2 : tasks[-1 - f.second].esucc)
-                if (--indeg[s2] == 0) make_ready(s2);
-            continue;
-        }
-        if (rank_of[f.second] >= 0) freew[rank_of[f.second]]++;
-        for (int s2 : tasks[f.second].succ)
-            if (--indeg[s2] == 0) make_ready(s2);
-    }
-    S.est_us = now;
-    S.W = W;
-    if (split)
-        for (auto& l : S.lists) order_tparts(l);
-    return S;
-}
-
-struct Params {
-    // r01i sweep (scripts/sched_sweep.sh): at N = 16384 W = 64 with no single-panel tail is
-    // 1.6-2.0% faster than W = 32, near = 1; at N = 4096 (chain-bound) near = 1 stays 6% faster
-    int W = 64, near = -1;  // near < 0: by size (near_for)
-    int ratio = -1;         // chunk-width rule of tile_chunks: < 0 picked per shape by the simulation
-    int split = 1;          // f64: the split diagonal step (TPART tasks); GPRX_PT_SPLIT=0 turns it off
-    int tail = 0;           // > 0: the capped chunk rule only in the last `tail` column blocks
-    int pair = -1;          // paired updates (make_schedule): < 0 the precision's default (default_pair),
-                            // 0 off, n > 0 pairs from row j + n (GPRX_PT_PAIR)
-    int label = 1;          // the narrow label row (make_schedule narrow, tile_gemm_rows16) where a fit has
-                            // at most LAB_NARROW labels; GPRX_PT_LABEL=0: the full tile and its pairing (A/B)
-    Cost cm;
-    int near_for(int nc) const { return near >= 0 ? near : (nc <= 64 ? 1 : 0); }
-    Params() {
-        if (const char* e = std::getenv("GPRX_PT_W")) W = std::max(1, std::atoi(e));
-        if (const char* e = std::getenv("GPRX_PT_NEAR")) near = std::max(0, std::atoi(e));
-        if (const char* e = std::getenv("GPRX_PT_RATIO")) ratio = std::max(0, std::atoi(e));
-        if (const char* e = std::getenv("GPRX_PT_DIAGX_US")) cm.diagx = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_TRSM_US")) cm.trsm = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_K128_US")) cm.k128 = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_OVH_US")) cm.ovh = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_BUILD_US")) cm.build = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_SPLIT")) split = std::atoi(e);
-        if (const char* e = std::getenv("GPRX_PT_TAIL")) tail = std::atoi(e);
-        if (const char* e = std::getenv("GPRX_PT_PAIR")) pair = std::atoi(e);
-        if (const char* e = std::getenv("GPRX_PT_TALL")) cm.tall = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_PAIR_NBMIN")) cm.pair_nbmin = std::max(1, std::atoi(e));
-        if (const char* e = std::getenv("GPRX_PT_PAIR_TAIL")) cm.pair_tail = std::max(0, std::atoi(e));
-        if (const char* e = std::getenv("GPRX_PT_TPART_US")) cm.tpart = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_DIAGXS_US")) cm.diagx_s = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_TPARTP_US")) cm.tpart_prog = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_KLAB_US")) cm.klab = std::atof(e);
-        if (const char* e = std::getenv("GPRX_PT_LABEL")) label = std::atoi(e);
-    }
-    // the cost model for a precision: the progressive parts are the f64 look-ahead factor's
-    Cost cost(bool f64) const {
-        Cost c = cm;
-        c.prog = f64 && DIAG_LA && !tp_linv_form();
-        c.np = tp_parts(f64 && DIAG_LA);
-        return c;
-    }
-};
-static const Params& params() {
-    static Params p;
-    return p;
-}
-
-// the chunk rule with the shortest simulated makespan: the fixed rule (ratio 0), or a capped
-// rule (ratio 8, 4, 2: width capped by the distance to the tile's last panel) on every tile or
-// only on the last 16 / 32 column blocks -- where the chain-bound tail waits for the diagonal
-// tiles' last wide chunks (N = 16384: ratio 2 on the last 16 blocks 25.46 -> 25.15 ms, the
-// simulation ranks it first too) -- unless GPRX_PT_RATIO fixes it (GPRX_PT_TAIL its reach)
-static const int kRatios[] = {0, 8, 4, 2};
-static const int kTails[] = {0, 16, 32};
-// Paired updates (T_UPD2) by precision, from same-box A/Bs (profiles/r06f_pair_ab.txt,
-// r06lno_pair_sweep.txt, r06uv_pair_tune.txt): rows from j + 4 (f64) / j + 2 (f32), chunks of at
-// least 4 panels, not in the last 32 (f64) / 16 (f32) columns -- C3's launch 25.49-25.63 ->
-// 24.68-24.85 ms (pairing every chunk: 25.77; every chunk of >= 16 panels before the last 64
-// columns: 25.01-25.07; rows from j + 3 or j + 6, >= 2 panels, the last 24 or 40 columns: within
-// 0.3% of the default), C4's f32 factor 99.26 -> 95.23-95.26 ms (rows from j + 4: 95.5).  Pairs delay their consumers (both rows wait for the later one), which the
-// narrow pieces near a tile's last panel and the chain-bound last columns cannot afford; the bulk
-// gains the wider mainloop.  GPRX_PT_PAIR / _NBMIN / _TAIL override.
-struct PairRule {
-    int pair, nbmin, tail;
-};
-static PairRule default_pair(bool f64) { return f64 ? PairRule{4, 4, 32} : PairRule{2, 4, 16}; }
-static Schedule best_schedule(int nc, int nr, const Params& pr, int P, bool build, int ni, bool split, bool f64,
-                              bool narrow = false) {
-    Cost cm = pr.cost(f64);
-    const PairRule pd = default_pair(f64);
-    if (!std::getenv("GPRX_PT_PAIR_NBMIN")) cm.pair_nbmin = pd.nbmin;
-    // with the inverse riding along (ni > 0, the LML) the factor's last columns are not the end of
-    // the launch -- the identity rows' updates follow them -- so they pair too: the LML's factor
-    // launch 46.83-47.00 -> 46.42-46.57 ms (last 16 columns spared: 46.49-46.60; same box,
-    // profiles/r06ls_lml_pair_sweep.txt)
-    if (!std::getenv("GPRX_PT_PAIR_TAIL")) cm.pair_tail = ni > 0 ? 0 : pd.tail;
-    Schedule best;
-    bool have = false;
-    const int want = pr.pair >= 0 ? pr.pair : pd.pair;
-    for (int pq : {want}) {
-        auto consider = [&](Schedule&& S) {
-            // a rule with more tasks (or the paired form) must win by > 0.5%
-            if (!have || S.est_us < best.est_us * 0.995) {
-                best = std::move(S);
-                have = true;
-            }
-        };
-        if (pr.ratio >= 0) {
-            consider(make_schedule(nc, nr, pr.W, pr.near_for(nc), P, cm, build, ni, pr.ratio, split, pr.tail, pq, narrow));
-            continue;
-        }
-        for (int r : kRatios)
-            for (int tl : kTails) {
-                if ((r == 0 && tl) || (tl && tl >= nc)) continue;
-                consider(make_schedule(nc, nr, pr.W, pr.near_for(nc), P, cm, build, ni, r, split, tl, pq, narrow));
-            }
-    }
-    return best;
-}
-
-// the split diagonal step runs for both precisions (f64: S through the look-ahead factor's LDS
-// image; f32: S in place for the rank-8 factor), unless GPRX_PT_SPLIT=0
-static bool split_for(bool f64) { (void)f64; return SPLIT_CODE && params().split != 0; }
-// (the parts of a step wait for each other: at least tp_parts workgroups)
-static bool split_for(bool f64, int P) { return P >= tp_parts(f64 && DIAG_LA) && split_for(f64); }
-
 }  // namespace pt
 
 // Per-context state: cached schedules (host + device copies) and the counter block.
@@ -3658,22 +2878,7 @@ void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info
     GPRX_HIP(hipGetLastError());
 }
 
-// ---- distributed factorisation: per-rank ticket lists and one rank's launch ------------------
-DistSched potrf_dist_schedule(int nc, int g, int gb, int ww, int P, bool build, bool inv, int ratio, bool f64, int tail) {
-    const pt::Params& pr = pt::params();
-    // a push: one tile's stores over xGMI plus the flag (measured on one GPU as a same-device
-    // copy; GPRX_DIST_PUSH_US / GPRX_DIST_REL_US override)
-    double push_us = 4.0, rel_us = 2.0;
-    if (const char* e = std::getenv("GPRX_DIST_PUSH_US")) push_us = std::atof(e);
-    if (const char* e = std::getenv("GPRX_DIST_REL_US")) rel_us = std::atof(e);
-    ww = std::max(2, std::min(ww, nc));
-    // update chunks at most half a window wide (flow control, make_schedule_dist), powers of two
-    int W = 1;
-    while (2 * W <= std::min(pr.W, std::max(1, ww / 2))) W *= 2;
-    return pt::make_schedule_dist(nc, inv, W, pr.near_for(nc), P, g, std::max(1, gb), ww, pr.cost(f64), build, push_us, rel_us,
-                                  pr.ratio >= 0 ? pr.ratio : ratio, pt::split_for(f64, P), pr.ratio >= 0 ? pr.tail : tail);
-}
-
+// ---- distributed factorisation: one rank's launch ------------------------------------------------
 template <typename T>
 void potrf_tiles_dist_launch(const DistLaunch<T>& L) {
     using namespace pt;
@@ -3715,29 +2920,6 @@ void potrf_tiles_dist_launch(const DistLaunch<T>& L) {
 }
 template void potrf_tiles_dist_launch<double>(const DistLaunch<double>&);
 template void potrf_tiles_dist_launch<float>(const DistLaunch<float>&);
-
-// Host-only schedule statistics (no device work): tasks, predicted makespan, and a check
-// that every task's producers come earlier in the ticket order.
-int64_t potrf_tiles_schedule_stats(int nc, int nr, int P, bool build, double* est_us, int ni, int ratio,
-                                   int32_t* list_out, int64_t list_max, int pair, bool narrow) {
-    if (nc < 1 || nr < nc || P < 1 || ni < 0 || ni > nr - nc)
-        throw Error{GPRX_ERR_ARG, "potrf tile schedule: need nc >= 1, nr >= nc + ni, P >= 1"};
-    pt::Params pr = pt::params();
-    if (pair >= 0) pr.pair = pair;
-    const bool split = pt::split_for(true, P);  // the f64 schedule
-    pt::Schedule S = ratio >= 0 ? pt::make_schedule(nc, nr, pr.W, pr.near_for(nc), P, pr.cost(true), build, ni, ratio, split,
-                                                    pr.tail, pr.pair > 0 ? pr.pair : 0, narrow)
-                                : pt::best_schedule(nc, nr, pr, P, build, ni, split, true, narrow);
-    if (est_us) *est_us = S.est_us;
-    if (list_out)  // the ticket list: {type | nb << 8, i, j, b0} per ticket
-        for (int64_t q = 0; q < (int64_t)S.list.size() && q < list_max; q++) {
-            const int4 t = S.list[q];
-            list_out[4 * q] = t.x, list_out[4 * q + 1] = t.y, list_out[4 * q + 2] = t.z, list_out[4 * q + 3] = t.w;
-        }
-    return S.ntasks;
-}
-
-bool potrf_split_for(bool f64, int P) { return pt::split_for(f64, P); }
 
 template void potrf_tiles<double>(double*, int64_t, int64_t, int64_t, double*, int*, Exec&, const TileBuild<double>*,
                                   int, bool, int);

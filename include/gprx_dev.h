@@ -27,7 +27,8 @@ gprx_status gprx_dev_bench(gprx_ctx* ctx, gprx_dtype dtype, int32_t what, int64_
 /* Host-only: build the tile-dataflow potrf schedule for nc diagonal blocks, nr row blocks
  * and P workers (build bit 0: with the fused covariance-build tasks; bit 1: the last nc of
  * the nr row blocks are identity rows, the inverse riding along; bit 2: the narrow label row --
- * row block nc, the only label block, updates as a 16-row product and leaves the pairs; bits 8..15: the update
+ * row block nc, the only label block, updates as a 16-row product and leaves the pairs; bit 3: the
+ * f32 schedule (its cost model, part count and pairing rule) instead of the f64 one; bits 8..15: the update
  * chunk rule's ratio + 1, 0 = the rule the simulated makespan picks; bits 16..23: the paired
  * updates' first row below the diagonal + 1, 1 = no pairs, 0 = the simulation's choice); returns its task count
  * and simulated makespan (us).  Throws nothing, needs no
@@ -40,12 +41,17 @@ gprx_status gprx_dev_schedule(int32_t nc, int32_t nr, int32_t P, int32_t build, 
 int64_t gprx_dev_schedule_list(int32_t nc, int32_t nr, int32_t P, int32_t build, int32_t* out, int64_t max);
 /* Host-only: the distributed factorisation's schedule (g ranks of P workers each, row blocks
  * grouped by gb, a window of ww panels; flags bit 0: with the fused covariance-build tasks,
- * bit 1: LML mode, the inverse's identity rows and the C = U U^T tiles riding along), simulated
+ * bit 1: LML mode, the inverse's identity rows and the C = U U^T tiles riding along, bit 3: the
+ * f32 schedule, bits 8..15: the update chunk rule's ratio + 1, 0 = the fixed rule), simulated
  * over all ranks with the pushes and window releases as timed nodes; returns the simulated
  * makespan (us), the update chunk width and the task count -- the figures gprx_dist.cpp picks
  * gb and ww by.  GPRX_ERR_ARG if the ticket order would violate a dependency. */
 gprx_status gprx_dev_dist_schedule(int32_t nc, int32_t P, int32_t g, int32_t gb, int32_t ww, int32_t flags,
                                    double* est_us, int32_t* chunk_w, int64_t* ntasks);
+/* Host-only: the ticket list of one rank of the same schedule, encoded as gprx_dev_schedule_list
+ * writes it, at most max tickets into out; returns the rank's task count, -1 on bad arguments. */
+int64_t gprx_dev_dist_schedule_list(int32_t nc, int32_t P, int32_t g, int32_t gb, int32_t ww, int32_t flags,
+                                    int32_t rank, int32_t* out, int64_t max);
 /* GPRX_PT_DEBUG=1: copy the per-workgroup status {ticket, phase, i, j} of the running (or last)
  * potrf_tiles launch out of pinned host memory, without synchronising; returns workgroups. */
 int32_t gprx_dev_pt_debug(int32_t* out, int32_t max_wg);

@@ -1,4 +1,4 @@
-"""Python model of the tile-dataflow Cholesky schedule (k_ptiles.hip make_schedule) for
+"""Python model of the tile-dataflow Cholesky schedule (pt_sched.cpp make_schedule) for
 exploring chunking rules and cost changes.  Unlike the C++ list scheduler it models the early
 publication of L_{k,k-1} inside DIAGX(k) (k_ptiles.hip: publish(lcnt+k, k) after the trsm
 phase), so chain estimates are closer to the device.

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Fit time under tile-schedule parameter variants (env knobs of k_ptiles.hip Params).
+# Fit time under tile-schedule parameter variants (env knobs of pt_sched.h Params).
 # Output: gpurun_out/sweep.log, one "<variant> <fits/s> <potrf avg us>" line per run.
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p $R/gpurun_out

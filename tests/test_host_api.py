@@ -8,7 +8,9 @@ KernelFactory<T>, Likelihood<T>, MatrixIO — driven through its two test execut
   reference's thresholds, plus a likelihood gradient consistency check, the sparse GP and
   PosteriorProcessTest 1-2 (Predict / operator() from 8 threads at once, on a fresh and on a
   loaded GP), and a user Kernel<T> subclass with no device form (host-evaluated through its
-  virtual operator(), factored on the device), all running their fits on the GPU."""
+  virtual operator(), factored on the device), all running their fits on the GPU.
+* pt_sched_test: not the host API but built and run the same way -- the tile schedule planner
+  (gpr_amd/csrc/pt_sched.cpp) linked alone, no libgprx and no HIP runtime."""
 import os
 import subprocess
 
@@ -40,6 +42,37 @@ def test_host_cpu():
     rc, lines, out = _run("host_cpu_test", *args)
     assert rc == 0, out
     assert len(lines) == 5 + len(args), out
+
+
+def test_schedule_planner_standalone():
+    """Every schedule of the frozen grid (tests/golden/make_schedule_digests.py), both precisions and
+    the sharded shapes: non-empty lists, a positive makespan, sharded tickets on row blocks their rank
+    owns, the split step's parts in their order (tests/cpp/pt_sched_test.cpp) -- and the figures it
+    prints equal the frozen ones."""
+    rc, lines, out = _run("pt_sched_test")
+    assert rc == 0, out
+    assert lines == ["PASS single-GPU schedules", "PASS sharded schedules"], out
+    # the program is built by the host compiler, the library by hipcc: the same planner source must
+    # give the frozen schedules under both (task counts and chunk width exactly, the makespan to
+    # 1e-12 relative, as tests/test_schedule_frozen.py)
+    import json
+    from tests.golden import make_schedule_digests as G
+    with open(G.FIXTURE) as f:
+        frozen = json.load(f)
+    got = {"single": {}, "sharded": {}}
+    for l in out.splitlines():
+        w = l.split()
+        if w and w[0] in got:
+            got[w[0]][w[1]] = w[2:]
+    assert sorted(got["single"]) == sorted(frozen["single"]) and sorted(got["sharded"]) == sorted(frozen["dist"])
+    for key, want in frozen["single"].items():
+        n, est = got["single"][key]
+        assert int(n) == want["ntasks"], key
+        assert abs(float(est) - float(want["est_us"])) <= 1e-12 * float(want["est_us"]), (key, est, want["est_us"])
+    for key, want in frozen["dist"].items():
+        n, w, est, *ranks = got["sharded"][key]
+        assert (int(n), int(w), [int(r) for r in ranks]) == (want["ntasks"], want["W"], want["rank_ntasks"]), key
+        assert abs(float(est) - float(want["est_us"])) <= 1e-12 * float(want["est_us"]), (key, est, want["est_us"])
 
 
 @pytest.mark.gpu

@@ -1,4 +1,4 @@
-"""Host-side checks of the tile-dataflow factorisation schedule (k_ptiles.hip make_schedule,
+"""Host-side checks of the tile-dataflow factorisation schedule (pt_sched.cpp make_schedule,
 exported as gprx_dev_schedule): every task's producers hold earlier tickets (the deadlock-freedom
 argument of the persistent kernel), task counts match the tile decomposition, and the simulated
 makespan behaves.  No device needed."""
@@ -15,7 +15,7 @@ from gpr_amd.gprx import lib
 def _sched(nc, nr, P=256, build=False, ident=False, ratio=0, pair=0):
     """ratio: the chunk rule (0 = the fixed rule, r > 0 = width capped at r x the panels left,
     None = the rule the simulated makespan picks); pair: paired updates from row j + pair (0 =
-    none, None = the f64 default, k_ptiles.hip default_pair)."""
+    none, None = the f64 default, pt_sched.cpp default_pair)."""
     L = lib()
     L.gprx_dev_schedule.argtypes = [ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                     ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int64)]
@@ -27,10 +27,10 @@ def _sched(nc, nr, P=256, build=False, ident=False, ratio=0, pair=0):
     return st, n.value, est.value
 
 
-W_DEF = 64  # k_ptiles.hip Params defaults: update chunk width, single-panel tail by size
+W_DEF = 64  # pt_sched.h Params defaults: update chunk width, single-panel tail by size
 
 
-NPARTS = 8  # TPART tasks per split step of the f64 schedule (k_ptiles.hip tp_parts)
+NPARTS = 8  # TPART tasks per split step of the f64 schedule (pt_sched.h tp_parts)
 
 
 def tparts(nc):
@@ -43,7 +43,7 @@ def near_def(nc):
 
 
 def _expected_tasks(nc, nr, W=W_DEF, near=None):
-    """Task count of the chunking rule (k_ptiles.hip tile_chunks): W-aligned chunks up to the
+    """Task count of the chunking rule (pt_sched.cpp tile_chunks): W-aligned chunks up to the
     last multiple of W at or before column j, then power-of-two pieces before the last `near`
     panels, then single panels."""
     near = near_def(nc) if near is None else near
@@ -69,7 +69,7 @@ def _expected_tasks(nc, nr, W=W_DEF, near=None):
 
 
 def _ratio_chunks(e, W, near, ratio):
-    """k_ptiles.hip tile_chunks with ratio > 0: greedy widest power-of-two piece p <= W
+    """pt_sched.cpp tile_chunks with ratio > 0: greedy widest power-of-two piece p <= W
     (W-aligned when p == W) ending >= near panels before e with p <= ratio x the panels left."""
     out, b = [], 0
     while b < e:
@@ -147,7 +147,7 @@ def test_schedule_with_fused_build(nc):
 
 @pytest.mark.parametrize("nc,extra", [(1, 1), (3, 1), (9, 1), (40, 1)])
 def test_schedule_with_identity_rows(nc, extra):
-    """The inverse riding along (k_ptiles.hip make_schedule ni > 0): identity row block a
+    """The inverse riding along (pt_sched.cpp make_schedule ni > 0): identity row block a
     gets TRSM(., k) only for k >= a and updates only from panel a on; the ticket order still
     respects every dependency, and the extra tasks match that count."""
     nr = nc + extra + nc
@@ -274,7 +274,7 @@ def _sched_list(nc, nr, P=256, ratio=None, ident=False):
 @pytest.mark.parametrize("nc,ratio,ident", [(2, None, False), (9, 0, False), (33, 2, False), (40, 0, True),
                                             (128, None, False)])
 def test_schedule_split_step_ticket_order(nc, ratio, ident):
-    """The split diagonal step's deadlock-freedom argument (k_ptiles.hip order_tparts): the eight
+    """The split diagonal step's deadlock-freedom argument (pt_sched.cpp order_tparts): the eight
     TPART(k, c) tickets come in the order c = 7, .., 0, after DIAGX(k - 1) and before DIAGX(k),
     and no other k's parts lie between them -- so at most seven workgroups ever wait on a
     sibling part and P >= 8 workers always leave one to claim the next ticket."""
@@ -315,7 +315,7 @@ def _sched_list_pair(nc, nr, build=True, ratio=0, pair=0, ident=False):
 
 @pytest.mark.parametrize("nc,pair", [(2, 1), (9, 1), (9, 2), (33, 2), (40, 4), (128, 2)])
 def test_schedule_paired_updates(nc, pair):
-    """Paired updates (T_UPD2, k_ptiles.hip make_schedule pair > 0): the off-diagonal tiles of
+    """Paired updates (T_UPD2, pt_sched.cpp make_schedule pair > 0): the off-diagonal tiles of
     column j from row j + pair down to the label row go in vertical pairs, each pair's (identical)
     chunks as one task; every tile's panels are still applied exactly once, in order, by tickets
     that come after the producers of their operands (replayed here), the identity rows and the
@@ -366,7 +366,7 @@ def test_schedule_paired_updates(nc, pair):
 
 
 def test_schedule_default_pairing_rule():
-    """The f64 default (k_ptiles.hip default_pair: rows from j + 4, chunks of >= 4 panels, not in
+    """The f64 default (pt_sched.cpp default_pair: rows from j + 4, chunks of >= 4 panels, not in
     the last 32 columns) at C3's shape: a valid ticket order with paired tasks, none of them in the
     last 32 column blocks or narrower than 4 panels; at C2's shape (32 column blocks) no pairs."""
     st, n, est = _sched(128, 129, build=True, ratio=None, pair=None)
@@ -382,7 +382,7 @@ def test_schedule_default_pairing_rule():
 
 @pytest.mark.parametrize("nc,pair", [(3, 1), (9, 2), (40, 4), (65, 4)])
 def test_schedule_paired_identity_rows(nc, pair):
-    """The LML mode with pairs (k_ptiles.hip make_schedule ident_even): identity row blocks go
+    """The LML mode with pairs (pt_sched.cpp make_schedule ident_even): identity row blocks go
     in pairs (E_2s, E_2s+1), both updating from panel 2s -- the odd row's block at column 2s is
     the zero tile potrf_tiles stores, so it has no producer; every other tile's panels are applied
     once, in order, after their operands are final; the odd rows' TRSMs still start at their own

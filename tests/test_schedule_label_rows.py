@@ -1,4 +1,4 @@
-"""Host-side checks of the narrow label row in the tile-dataflow schedule (k_ptiles.hip
+"""Host-side checks of the narrow label row in the tile-dataflow schedule (pt_sched.cpp
 make_schedule `narrow`, flag bit 2 of gprx_dev_schedule / gprx_dev_schedule_list): the label row
 block nc updates as a 16-row product, so it is never the bottom of a paired update -- row nc - 1
 runs single in the columns where it was the label row's top.  Task types, the meaning of a ticket
