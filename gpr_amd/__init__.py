@@ -5,11 +5,11 @@ behind the C ABI of include/gprx.h).  This package holds the Python binding used
 tests and bench.py; the C++ host API mirroring the reference classes is in include/gpr/.
 """
 from . import kernels
-from .kernels import (Gaussian, GaussianExp, White, RationalQuadratic, Periodic, Sum, Product, parse_kernel,
+from .kernels import (Gaussian, GaussianExp, White, RationalQuadratic, Periodic, Matern32, Matern52, Sum, Product, parse_kernel,
                       general_kernel)
 from .gprx import (Context, DeviceArray, Model, GprxError, lib, device_count, unique_id, query_shard, LIB_PATH,
                    runtime_info)
 
-__all__ = ["DeviceArray", "kernels", "Gaussian", "GaussianExp", "White", "RationalQuadratic", "Periodic", "Sum", "Product",
+__all__ = ["DeviceArray", "kernels", "Gaussian", "GaussianExp", "White", "RationalQuadratic", "Periodic", "Matern32", "Matern52", "Sum", "Product",
            "parse_kernel", "general_kernel", "Context", "Model", "GprxError", "lib", "device_count", "unique_id", "LIB_PATH",
            "runtime_info"]

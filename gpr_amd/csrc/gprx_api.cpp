@@ -61,6 +61,8 @@ static int leaf_nparams(int op) {
     switch (op) {
         case GPRX_K_GAUSSIAN:
         case GPRX_K_GAUSSIAN_EXP:
+        case GPRX_K_MATERN32:
+        case GPRX_K_MATERN52:
             return 2;
         case GPRX_K_WHITE:
             return 1;
@@ -147,6 +149,23 @@ std::string canonicalize(const gprx_kernel_desc& desc, KCanon<T>& K) {
                 nper++;
                 L.c0 = p0 * p0;
                 L.c1 = T(-0.5) / (p2 * p2);
+                break;
+            case GPRX_K_MATERN32:  // c0 (1 + a) exp(-a), a = sqrt(c1 r2)
+                if (p0 == T(0)) return "Matern32Kernel: sigma has to be positive";
+                if (p1 == T(0)) return "Matern32Kernel: scale has to be positive";
+                L.type = L_MATERN32;
+                L.c0 = p1 * p1;
+                L.c1 = T(3) / (p0 * p0);
+                r2 = true;
+                break;
+            case GPRX_K_MATERN52:  // c0 (1 + a + a^2/3) exp(-a)
+                if (p0 == T(0)) return "Matern52Kernel: sigma has to be positive";
+                if (p1 == T(0)) return "Matern52Kernel: scale has to be positive";
+                L.type = L_MATERN52;
+                L.c0 = p1 * p1;
+                L.c1 = T(5) / (p0 * p0);
+                L.c2 = L.c0 / T(3);
+                r2 = true;
                 break;
         }
         // the folded exp constants (fexp_fold: f64 predict epilogue only)
@@ -1704,7 +1723,7 @@ static gprx_status model_lml(gprx_model* M, uint32_t flags, double* value, doubl
         download(acc, M->grad.p, sizeof(acc), s);
         for (int l = 0; l < K.nleaf; l++) {
             const int t = K.leaf[l].type;
-            const int np = (t == L_WHITE) ? 1 : ((t == L_GAUSS || t == L_GAUSS_EXP) ? 2 : 3);
+            const int np = leaf_type_nparams(t);
             for (int q = 0; q < np; q++) grad[K.param_base[l] + q] = 0.5 * acc[l * 3 + q];
         }
     }
@@ -2462,7 +2481,7 @@ static gprx_status sparse_lml_impl(gprx_ctx* ctx, const gprx_kernel_desc* desc, 
     if (want_grad) {
         for (int l = 0; l < K.nleaf; l++) {
             const int t = K.leaf[l].type;
-            const int npl = (t == L_WHITE) ? 1 : ((t == L_GAUSS || t == L_GAUSS_EXP) ? 2 : 3);
+            const int npl = leaf_type_nparams(t);
             for (int q = 0; q < npl; q++) grad[K.param_base[l] + q] = acc_x[l * 3 + q];
         }
     }

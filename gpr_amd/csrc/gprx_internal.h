@@ -7,7 +7,7 @@
 // the host into a SUM OF PRODUCTS OF LEAVES: k = sum_t prod_{l in t} leaf_l.  Every leaf
 // depends on the pair only through a few streaming statistics that are accumulated over
 // the d input dimensions in one pass:
-//     r2        = sum_k (x_k - y_k)^2                 (Gaussian, GaussianExp, RQ, White)
+//     r2        = sum_k (x_k - y_k)^2                 (Gaussian, GaussianExp, RQ, White, Matern)
 //     S_p       = sum_k sin^2(b_p (x_k - y_k))         (Periodic leaf p)
 //     F_p       = sum_k 2 (x_k-y_k) sin cos(b_p(...))  (Periodic d/db, gradient only)
 // sin(b(x-y)) is formed from per-sample sin/cos tables (sin(bx)cos(by) - cos(bx)sin(by)),
@@ -31,7 +31,24 @@ constexpr int MAX_LEAF = 8;
 constexpr int MAX_TERM = 16;
 constexpr int MAX_PER = 2;  // periodic leaves with distinct tables
 
-enum LeafType { L_GAUSS = 1, L_GAUSS_EXP = 2, L_WHITE = 3, L_RQ = 4, L_PERIODIC = 5 };
+enum LeafType { L_GAUSS = 1, L_GAUSS_EXP = 2, L_WHITE = 3, L_RQ = 4, L_PERIODIC = 5, L_MATERN32 = 6, L_MATERN52 = 7 };
+
+// parameters (and gradient slots) of a leaf
+__host__ __device__ inline int leaf_type_nparams(int type) {
+    switch (type) {
+        case L_WHITE:
+            return 1;
+        case L_GAUSS:
+        case L_GAUSS_EXP:
+        case L_MATERN32:
+        case L_MATERN52:
+            return 2;
+        case L_RQ:
+        case L_PERIODIC:
+            return 3;
+    }
+    return 0;
+}
 
 template <typename T>
 struct KLeaf {
@@ -71,7 +88,17 @@ std::string canonicalize(const gprx_kernel_desc& desc, KCanon<T>& out);
 //   White          r2 == 0 ? s^2 : 0 (exact equality)               :695-702
 //   RQ             s^2 (1 + 0.5 r2 / (sigma^2 alpha))^(-alpha)      :794-797
 //   Periodic       s^2 exp(-0.5 S / sigma^2)                        :912-920
+// and, not in the reference (a = sqrt(c1 r2), c0 = s^2):
+//   Matern32       s^2 (1 + a) exp(-a),           c1 = 3 / sigma^2
+//   Matern52       s^2 (1 + a + a^2/3) exp(-a),   c1 = 5 / sigma^2, c2 = c0 / 3
+// The MFMA paths hand in r2 from the norm expansion, which rounding can leave at about
+// -1e-16 (predict: pair_stats_nc): the root's argument is clamped at 0, NaN kept.
 // ---------------------------------------------------------------------------------
+template <typename T>
+__host__ __device__ inline T matern_arg(T c1, T r2) {  // a = sqrt(c1 max(r2, 0)); NaN stays NaN
+    const T x = c1 * r2;
+    return sqrt(x < T(0) ? T(0) : x);
+}
 template <typename T>
 __host__ __device__ inline T leaf_value(const KLeaf<T>& L, T r2, T s0, T s1) {
     switch (L.type) {
@@ -84,6 +111,14 @@ __host__ __device__ inline T leaf_value(const KLeaf<T>& L, T r2, T s0, T s1) {
             return (L.c2 == T(1)) ? L.c0 / (T(1) + L.c1 * r2) : L.c0 * exp(-L.c2 * log1p(L.c1 * r2));
         case L_PERIODIC:
             return L.c0 * exp(L.c1 * (L.pslot == 0 ? s0 : s1));
+        case L_MATERN32: {
+            const T a = matern_arg(L.c1, r2);
+            return fma(L.c0, a, L.c0) * exp(-a);
+        }
+        case L_MATERN52: {
+            const T a = matern_arg(L.c1, r2);
+            return fma(a, fma(a, L.c2, L.c0), L.c0) * exp(-a);
+        }
     }
     return T(0);
 }
@@ -132,6 +167,22 @@ __host__ __device__ inline void leaf_grad(const KLeaf<T>& L, T r2, T s0, T s1, T
             g[0] = T(2) * sc * e;
             g[1] = T(-0.5) * sc * sc * e * fb / (sig * sig);
             g[2] = sc * sc * e * s / (sig * sig * sig);
+            return;
+        }
+        case L_MATERN32: {  // p = (sigma, scale): (s^2 a^2 e / sigma, 2 s (1 + a) e), e = exp(-a)
+            T sig = L.p[0], sc = L.p[1];
+            T a = matern_arg(L.c1, r2), e = exp(-a);
+            g[0] = sc * sc * a * a * e / sig;
+            g[1] = T(2) * sc * (T(1) + a) * e;
+            g[2] = 0;
+            return;
+        }
+        case L_MATERN52: {  // (s^2 (a^2/3) (1 + a) e / sigma, 2 s (1 + a + a^2/3) e)
+            T sig = L.p[0], sc = L.p[1];
+            T a = matern_arg(L.c1, r2), e = exp(-a);
+            g[0] = sc * sc * (a * a * (T(1) / T(3))) * (T(1) + a) * e / sig;
+            g[1] = T(2) * sc * fma(a, fma(a, T(1) / T(3), T(1)), T(1)) * e;
+            g[2] = 0;
             return;
         }
     }

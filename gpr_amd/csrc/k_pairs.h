@@ -36,7 +36,10 @@ static inline int kp_of(const KCanon<T>& K, int d) {  // MFMA depth of the perio
 // FOLD (f64 predict): exp leaves with fold set take fexp_fold(f1 x + f0), which also carries
 // the leaf's scale; SET: the first leaf of a sum writes p (0 + x and 1 x are exact: the same
 // bits as adding to 0 / multiplying 1, one instruction less per pair).
-template <typename T, int E, bool MUL, bool FOLD = false, bool SET = false>
+// MAT: the tree holds a Matern leaf (chosen on the host, as the kernels' NPER and R2): the
+// square-root branches are compiled only into the kernels such trees launch, so the others
+// keep their code and registers.
+template <typename T, int E, bool MUL, bool FOLD = false, bool SET = false, bool MAT = false>
 __device__ __forceinline__ void leaf_into(const KLeaf<T>* __restrict__ L, const T (&r2)[E], const T (&s)[E],
                                           T (&p)[E]) {
     const int ty = L->type;
@@ -77,6 +80,21 @@ __device__ __forceinline__ void leaf_into(const KLeaf<T>* __restrict__ L, const 
                 p[e] = MUL ? p[e] * f : p[e] + f;
             }
         }
+    } else if (MAT && ty == L_MATERN32) {  // c0 (1 + a) exp(-a), a = sqrt(c1 r2): matern_arg clamps the
+        // unclamped predict statistic (pair_stats_nc, r2 ~ -1e-16 on a training point) at 0
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const T a = matern_arg(c1, r2[e]);
+            const T f = fma(c0, a, c0) * fexp(-a);
+            p[e] = MUL ? p[e] * f : p[e] + f;
+        }
+    } else if (MAT && ty == L_MATERN52) {  // c0 (1 + a + a^2/3) exp(-a); c2 = c0 / 3
+#pragma unroll
+        for (int e = 0; e < E; e++) {
+            const T a = matern_arg(c1, r2[e]);
+            const T f = fma(a, fma(a, c2, c0), c0) * fexp(-a);
+            p[e] = MUL ? p[e] * f : p[e] + f;
+        }
     } else {  // L_GAUSS, L_GAUSS_EXP
 #pragma unroll
         for (int e = 0; e < E; e++) {
@@ -86,21 +104,21 @@ __device__ __forceinline__ void leaf_into(const KLeaf<T>* __restrict__ L, const 
     }
 }
 
-template <typename T, int E, bool FOLD = false>
+template <typename T, int E, bool FOLD = false, bool MAT = false>
 __device__ __forceinline__ void pair_values(const KCanon<T>* __restrict__ K, const T (&r2)[E], const T (&s)[E],
                                             T (&v)[E]) {
     const int nl = K->nleaf;
     if (FOLD && K->sum_leaves) {  // (nl >= 1: the first leaf writes v)
-        leaf_into<T, E, false, true, true>(&K->leaf[0], r2, s, v);
+        leaf_into<T, E, false, true, true, MAT>(&K->leaf[0], r2, s, v);
 #pragma unroll 1
-        for (int l = 1; l < nl; l++) leaf_into<T, E, false, true>(&K->leaf[l], r2, s, v);
+        for (int l = 1; l < nl; l++) leaf_into<T, E, false, true, false, MAT>(&K->leaf[l], r2, s, v);
         return;
     }
 #pragma unroll
     for (int e = 0; e < E; e++) v[e] = 0;
     if (K->sum_leaves) {
 #pragma unroll 1
-        for (int l = 0; l < nl; l++) leaf_into<T, E, false>(&K->leaf[l], r2, s, v);
+        for (int l = 0; l < nl; l++) leaf_into<T, E, false, false, false, MAT>(&K->leaf[l], r2, s, v);
         return;
     }
     const int nt = K->nterm;
@@ -112,7 +130,7 @@ __device__ __forceinline__ void pair_values(const KCanon<T>* __restrict__ K, con
         for (int e = 0; e < E; e++) p[e] = 1;
 #pragma unroll 1
         for (int l = 0; l < nl; l++)
-            if (msk & (1u << l)) leaf_into<T, E, true>(&K->leaf[l], r2, s, p);
+            if (msk & (1u << l)) leaf_into<T, E, true, false, false, MAT>(&K->leaf[l], r2, s, p);
 #pragma unroll
         for (int e = 0; e < E; e++) v[e] += p[e];
     }
@@ -161,7 +179,7 @@ __device__ __forceinline__ void pair_stats_nc(T pr2, T pper, T nu, T nv, T hd, T
 // Tile (i0, j0) of K(X, X) (+ sigma2 on the diagonal, identity beyond n) into A
 // (column-major), from the features FU, FV (nf rows); plain stores of the lower triangle.
 // Returns whether any of this thread's values is not finite.
-template <typename T, int NPER, bool R2>
+template <typename T, int NPER, bool R2, bool MAT = false>
 __device__ __forceinline__ bool build_tile(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
                                            const T* __restrict__ FV, int64_t nf, int Kr, int Kp, T hd,
                                            T* __restrict__ A, int64_t ld, int64_t n, T sigma2, int64_t i0, int64_t j0,
@@ -201,7 +219,7 @@ __device__ __forceinline__ bool build_tile(const KCanon<T>* __restrict__ Kd, con
                 r2[(reg - G * h) * 4 + y] = gi == gj ? T(0) : a;
                 sp[(reg - G * h) * 4 + y] = gi == gj ? T(0) : b;
             }
-        pair_values<T, 4 * G>(Kd, r2, sp, v);
+        pair_values<T, 4 * G, false, MAT>(Kd, r2, sp, v);
 #pragma unroll
         for (int reg = G * h; reg < G * h + G; reg++) {
             const int64_t gj = j0 + wc * 32 + x * 16 + Tr::orow(lk, reg);
@@ -234,7 +252,7 @@ __device__ __forceinline__ bool build_tile(const KCanon<T>* __restrict__ Kd, con
 // With Y (one label column, nb entries): also ky[r] = sum over this tile's columns j of
 // K(a_{i0+r}, b_j) Y[j], r < 128 (rows >= na get 0) -- the sparse fit's Kmn Y without a
 // 128-row label tile in the rank-k accumulation.
-template <typename T, int NPER, bool R2>
+template <typename T, int NPER, bool R2, bool MAT = false>
 __device__ __forceinline__ bool cross_tile(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU, int64_t nfu,
                                            int64_t na, const T* __restrict__ FV, int64_t nfv, int64_t nb, int Kr,
                                            int Kp, T hd, T* __restrict__ A, int64_t ld, int64_t i0, int64_t j0,
@@ -269,7 +287,7 @@ __device__ __forceinline__ bool cross_tile(const KCanon<T>* __restrict__ Kd, con
                 r2[(reg - G * h) * 4 + y] = a;
                 sp[(reg - G * h) * 4 + y] = b;
             }
-        pair_values<T, 4 * G>(Kd, r2, sp, v);
+        pair_values<T, 4 * G, false, MAT>(Kd, r2, sp, v);
 #pragma unroll
         for (int reg = G * h; reg < G * h + G; reg++) {
             const int64_t gj = j0 + wc * 32 + x * 16 + Tr::orow(lk, reg);

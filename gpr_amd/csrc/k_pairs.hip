@@ -4,7 +4,7 @@
 // GaussianProcess::ComputeKernelMatrixInternal (lib/GaussianProcess.cpp:384-402) with
 // AddNoiseToKernelMatrix (:375-381), and the per-query kernel vector of Predict
 // (lib/GaussianProcess.cpp:54-61, 684-693) -- for kernel trees whose leaves are Gaussian,
-// GaussianExp, RationalQuadratic and at most one Periodic frequency (no White leaf, which
+// GaussianExp, RationalQuadratic, Matern 3/2 and 5/2 and at most one Periodic frequency (no White leaf, which
 // needs the exact test r2 == 0, include/Kernel.h:696).
 //
 // Every leaf depends on a pair only through r2 = sum_k (x_k - y_k)^2 and
@@ -67,11 +67,13 @@ __global__ void features_kernel(const T* __restrict__ X, int64_t n, int d, const
 }
 
 // Lower triangle of K(X, X) (+ sigma2 on the diagonal, identity padding) into A (column-major).
-template <typename T, int NPER, bool R2>
-__global__ __launch_bounds__(NT) void kbuild_mma_kernel(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
-                                                        const T* __restrict__ FV,
-                                                        int64_t nf, int Kr, int Kp, T hd, T* __restrict__ A,
-                                                        int64_t ld, int64_t n, T sigma2, int* __restrict__ flag) {
+// (Every kernel of this file comes in two forms from one body: X_kernel for trees without a
+// Matern leaf and X_kernel_m, MAT = true, for trees with one; k_pairs.h leaf_into.)
+template <typename T, int NPER, bool R2, bool MAT>
+__device__ __forceinline__ void kbuild_mma_body(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
+                                                const T* __restrict__ FV, int64_t nf, int Kr, int Kp, T hd,
+                                                T* __restrict__ A, int64_t ld, int64_t n, T sigma2,
+                                                int* __restrict__ flag) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* smem = reinterpret_cast<T*>(smem_raw);
     // the kernel tree is read from device memory (scalar loads): as a by-value kernel
@@ -85,27 +87,53 @@ __global__ __launch_bounds__(NT) void kbuild_mma_kernel(const KCanon<T>* __restr
         ti = i;
         tj = b - i * (i + 1) / 2;
     }
-    const bool bad = build_tile<T, NPER, R2>(Kd, FU, FV, nf, Kr, Kp, hd, A, ld, n, sigma2, ti * GT, tj * GT, smem,
-                                                    threadIdx.x);
+    const bool bad = build_tile<T, NPER, R2, MAT>(Kd, FU, FV, nf, Kr, Kp, hd, A, ld, n, sigma2, ti * GT, tj * GT, smem,
+                                                  threadIdx.x);
     if (bad) atomicOr(flag, 1);
 }
+#define GPRX_KBUILD_ARGS                                                                                         \
+    const KCanon<T>*__restrict__ Kd, const T *__restrict__ FU, const T *__restrict__ FV, int64_t nf, int Kr, int Kp, \
+        T hd, T *__restrict__ A, int64_t ld, int64_t n, T sigma2, int *__restrict__ flag
+template <typename T, int NPER, bool R2>
+__global__ __launch_bounds__(NT) void kbuild_mma_kernel(GPRX_KBUILD_ARGS) {
+    kbuild_mma_body<T, NPER, R2, false>(Kd, FU, FV, nf, Kr, Kp, hd, A, ld, n, sigma2, flag);
+}
+template <typename T, int NPER, bool R2>
+__global__ __launch_bounds__(NT) void kbuild_mma_kernel_m(GPRX_KBUILD_ARGS) {
+    kbuild_mma_body<T, NPER, R2, true>(Kd, FU, FV, nf, Kr, Kp, hd, A, ld, n, sigma2, flag);
+}
+#undef GPRX_KBUILD_ARGS
 
 // Cross matrix K(Xa, Xb) (na x nb) into A, one workgroup per 128x128 tile (grid.x over the
 // rows of Xa, grid.y over the rows of Xb).
-template <typename T, int NPER, bool R2>
-__global__ __launch_bounds__(NT) void kcross_mma_kernel(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
-                                                        int64_t nfu, int64_t na, const T* __restrict__ FV, int64_t nfv,
-                                                        int64_t nb, int Kr, int Kp, T hd, T* __restrict__ A, int64_t ld,
-                                                        int* __restrict__ flag, const T* __restrict__ Y,
-                                                        T* __restrict__ kyp) {
+template <typename T, int NPER, bool R2, bool MAT>
+__device__ __forceinline__ void kcross_mma_body(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
+                                                int64_t nfu, int64_t na, const T* __restrict__ FV, int64_t nfv,
+                                                int64_t nb, int Kr, int Kp, T hd, T* __restrict__ A, int64_t ld,
+                                                int* __restrict__ flag, const T* __restrict__ Y,
+                                                T* __restrict__ kyp) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* smem = reinterpret_cast<T*>(smem_raw);
     // kyp: per column tile, the tile rows' partial K Y (nfu entries per column tile)
     T* ky = Y ? kyp + (int64_t)blockIdx.y * nfu + (int64_t)blockIdx.x * GT : nullptr;
-    const bool bad = cross_tile<T, NPER, R2>(Kd, FU, nfu, na, FV, nfv, nb, Kr, Kp, hd, A, ld, (int64_t)blockIdx.x * GT,
-                                             (int64_t)blockIdx.y * GT, smem, threadIdx.x, Y, ky);
+    const bool bad = cross_tile<T, NPER, R2, MAT>(Kd, FU, nfu, na, FV, nfv, nb, Kr, Kp, hd, A, ld,
+                                                  (int64_t)blockIdx.x * GT, (int64_t)blockIdx.y * GT, smem, threadIdx.x,
+                                                  Y, ky);
     if (bad) atomicOr(flag, 1);
 }
+#define GPRX_KCROSS_ARGS                                                                                          \
+    const KCanon<T>*__restrict__ Kd, const T *__restrict__ FU, int64_t nfu, int64_t na, const T *__restrict__ FV, \
+        int64_t nfv, int64_t nb, int Kr, int Kp, T hd, T *__restrict__ A, int64_t ld, int *__restrict__ flag,     \
+        const T *__restrict__ Y, T *__restrict__ kyp
+template <typename T, int NPER, bool R2>
+__global__ __launch_bounds__(NT) void kcross_mma_kernel(GPRX_KCROSS_ARGS) {
+    kcross_mma_body<T, NPER, R2, false>(Kd, FU, nfu, na, FV, nfv, nb, Kr, Kp, hd, A, ld, flag, Y, kyp);
+}
+template <typename T, int NPER, bool R2>
+__global__ __launch_bounds__(NT) void kcross_mma_kernel_m(GPRX_KCROSS_ARGS) {
+    kcross_mma_body<T, NPER, R2, true>(Kd, FU, nfu, na, FV, nfv, nb, Kr, Kp, hd, A, ld, flag, Y, kyp);
+}
+#undef GPRX_KCROSS_ARGS
 
 // S[row0 + 0, i] += alpha sum_{c < nct} kyp[c * nfu + i] for i < na (the label row of the
 // sparse normal equations).  256 threads = 16 rows x 16 column-tile groups: group q sums
@@ -135,12 +163,11 @@ __global__ __launch_bounds__(256) void ky_reduce_kernel(const T* __restrict__ ky
 // more outputs per query would spill next to the two accumulator sets; they take the direct
 // kernel of k_predict.hip.)
 constexpr int PM = 1;
-template <typename T, int NPER, bool R2>
-__global__ __launch_bounds__(NT) void predict_mma_kernel(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
-                                                         int64_t nfu,
-                                                         const T* __restrict__ FV, int64_t nfv, int Kr, int Kp, T hd,
-                                                         const T* __restrict__ alpha, int64_t n, int m, int64_t q,
-                                                         T* __restrict__ mean) {
+template <typename T, int NPER, bool R2, bool MAT>
+__device__ __forceinline__ void predict_mma_body(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
+                                                 int64_t nfu, const T* __restrict__ FV, int64_t nfv, int Kr, int Kp,
+                                                 T hd, const T* __restrict__ alpha, int64_t n, int m, int64_t q,
+                                                 T* __restrict__ mean) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* smem = reinterpret_cast<T*>(smem_raw);
     typedef Mfma<T> Tr;
@@ -260,7 +287,7 @@ __global__ __launch_bounds__(NT) void predict_mma_kernel(const KCanon<T>* __rest
                     pair_stats_nc<T, NPER, R2>(R2 ? ar[x][y][reg] : T(0), NPER ? ap[x][y][reg] : T(0), nu[y],
                                                R2 ? nvb[jl] : T(0), hd, r2[4 * u + y], sp[4 * u + y]);
             }
-            pair_values<T, 8, true>(Kd, r2, sp, v);  // (folded exp leaves: k_pairs.h leaf_into)
+            pair_values<T, 8, true, MAT>(Kd, r2, sp, v);  // (folded exp leaves: k_pairs.h leaf_into)
 #pragma unroll
             for (int u = 0; u < 2; u++) {
                 const T al = alb[wc * 32 + x * 16 + Tr::orow(lk, 2 * h + u)];
@@ -301,6 +328,18 @@ __global__ __launch_bounds__(NT) void predict_mma_kernel(const KCanon<T>* __rest
         }
     }
 }
+#define GPRX_PREDICT_ARGS                                                                                          \
+    const KCanon<T>*__restrict__ Kd, const T *__restrict__ FU, int64_t nfu, const T *__restrict__ FV, int64_t nfv, \
+        int Kr, int Kp, T hd, const T *__restrict__ alpha, int64_t n, int m, int64_t q, T *__restrict__ mean
+template <typename T, int NPER, bool R2>
+__global__ __launch_bounds__(NT) void predict_mma_kernel(GPRX_PREDICT_ARGS) {
+    predict_mma_body<T, NPER, R2, false>(Kd, FU, nfu, FV, nfv, Kr, Kp, hd, alpha, n, m, q, mean);
+}
+template <typename T, int NPER, bool R2>
+__global__ __launch_bounds__(NT) void predict_mma_kernel_m(GPRX_PREDICT_ARGS) {
+    predict_mma_body<T, NPER, R2, true>(Kd, FU, nfu, FV, nfv, Kr, Kp, hd, alpha, n, m, q, mean);
+}
+#undef GPRX_PREDICT_ARGS
 
 // ---------------------------------------------------------------------------------------
 // LML gradient from pair statistics (replaces lml_grad_kernel, k_lml.hip, for sum-of-leaves
@@ -339,14 +378,13 @@ __global__ void grad_features_kernel(const T* __restrict__ X, int64_t n, int d, 
 // CROSS: every tile of a rectangular pair block (rows: the U features, nf rows, nrow live;
 // columns: the V features, nfv rows, ncol live) with weights w_ij = alpha_i beta_j - C_ij and
 // no diagonal (the sparse likelihood's sum over K(X, Xm), include/SparseLikelihood.h:317-340).
-template <typename T, int NPER, bool R2, bool CROSS = false>
-__global__ __launch_bounds__(NT) void grad_mma_kernel(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
-                                                      const T* __restrict__ FV, const T* __restrict__ GU,
-                                                      const T* __restrict__ GV, int64_t nf, int Kr, int Kp, int Kf,
-                                                      T hd, const T* __restrict__ alpha, const T* __restrict__ C,
-                                                      int64_t ldc, int64_t n, double* __restrict__ part,
-                                                      const uint64_t* __restrict__ ctab, int64_t nfv = 0,
-                                                      int64_t ncol = 0, const T* __restrict__ beta = nullptr) {
+template <typename T, int NPER, bool R2, bool CROSS, bool MAT>
+__device__ __forceinline__ void grad_mma_body(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
+                                              const T* __restrict__ FV, const T* __restrict__ GU,
+                                              const T* __restrict__ GV, int64_t nf, int Kr, int Kp, int Kf, T hd,
+                                              const T* __restrict__ alpha, const T* __restrict__ C, int64_t ldc,
+                                              int64_t n, double* __restrict__ part, const uint64_t* __restrict__ ctab,
+                                              int64_t nfv, int64_t ncol, const T* __restrict__ beta) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     T* smem = reinterpret_cast<T*>(smem_raw);
     double* sacc = reinterpret_cast<double*>(smem_raw + gemm_lds<T>());  // [8 waves][MAX_LEAF * 3]
@@ -473,6 +511,23 @@ __global__ __launch_bounds__(NT) void grad_mma_kernel(const KCanon<T>* __restric
                         a1 += (double)(we * m1);
                     }
                 });
+            } else if (MAT && (ty == L_MATERN32 || ty == L_MATERN52)) {
+                // p = (sigma, scale), a = sqrt(c1 r2), a^2 = c1 r2, e = exp(-a):
+                //   3/2: g = (sc^2 a^2 e / sig,             2 sc (1 + a) e)
+                //   5/2: g = (sc^2 (a^2/3) (1 + a) e / sig, 2 sc (1 + a + a^2/3) e)
+                const T sig = L.p[0], sc = L.p[1], c1 = L.c1;
+                const bool m5 = ty == L_MATERN52;
+                const T k0 = sc * sc / sig * (m5 ? c1 / T(3) : c1), k1 = T(2) * sc, k3 = m5 ? c1 / T(3) : T(0);
+                each([&](auto cc) {
+                    constexpr int x = decltype(cc)::value >> 2, reg = decltype(cc)::value & 3;
+#pragma unroll
+                    for (int y = 0; y < 4; y++) {
+                        const T r2 = ar[x][y][reg], a = sqrt(c1 * r2), we = wt[x][y][reg] * exp(-a);
+                        const T q1 = T(1) + a;
+                        a0 += (double)(we * (k0 * r2 * (m5 ? q1 : T(1))));
+                        a1 += (double)(we * (k1 * fma(k3, r2, q1)));
+                    }
+                });
             } else {  // L_RQ, p = (scale, sigma, alpha)
                 const T sc = L.p[0], sig = L.p[1], al = L.p[2];
                 const T kq = T(0.5) / (sig * sig * al), k0 = T(2) * sc, k1 = sc * sc / (sig * sig * sig), k2 = sc * sc;
@@ -539,6 +594,22 @@ __global__ __launch_bounds__(NT) void grad_mma_kernel(const KCanon<T>* __restric
         part[(int64_t)blockIdx.x * MAX_LEAF * 3 + t] = v;
     }
 }
+#define GPRX_GRAD_ARGS                                                                                             \
+    const KCanon<T>*__restrict__ Kd, const T *__restrict__ FU, const T *__restrict__ FV, const T *__restrict__ GU, \
+        const T *__restrict__ GV, int64_t nf, int Kr, int Kp, int Kf, T hd, const T *__restrict__ alpha,           \
+        const T *__restrict__ C, int64_t ldc, int64_t n, double *__restrict__ part,                                \
+        const uint64_t *__restrict__ ctab, int64_t nfv, int64_t ncol, const T *__restrict__ beta
+template <typename T, int NPER, bool R2, bool CROSS = false>
+__global__ __launch_bounds__(NT) void grad_mma_kernel(GPRX_GRAD_ARGS) {
+    grad_mma_body<T, NPER, R2, CROSS, false>(Kd, FU, FV, GU, GV, nf, Kr, Kp, Kf, hd, alpha, C, ldc, n, part, ctab, nfv,
+                                             ncol, beta);
+}
+template <typename T, int NPER, bool R2, bool CROSS = false>
+__global__ __launch_bounds__(NT) void grad_mma_kernel_m(GPRX_GRAD_ARGS) {
+    grad_mma_body<T, NPER, R2, CROSS, true>(Kd, FU, FV, GU, GV, nf, Kr, Kp, Kf, hd, alpha, C, ldc, n, part, ctab, nfv,
+                                            ncol, beta);
+}
+#undef GPRX_GRAD_ARGS
 
 // gout[p] = sum over tiles of part[tile][p], in tile order
 __global__ void grad_reduce_kernel(const double* __restrict__ part, int64_t ntiles, double* __restrict__ gout) {
@@ -580,6 +651,13 @@ void launch_pair_features(const KCanon<T>& K, const T* X, int64_t n, int d, cons
 }
 
 template <typename T>
+static bool has_matern(const KCanon<T>& K) {
+    for (int l = 0; l < K.nleaf; l++)
+        if (K.leaf[l].type == L_MATERN32 || K.leaf[l].type == L_MATERN52) return true;
+    return false;
+}
+
+template <typename T>
 static size_t pairs_lds() {
     const size_t a = mm::gemm_lds<T>() + sizeof(T) * 4 * GT, b = sizeof(T) * 4 * GT * pr::PM;  // + norms, alpha (x2)
     return a > b ? a : b;
@@ -593,9 +671,10 @@ static size_t pairs_lds() {
                                          (int)lds_));                                                \
             hipLaunchKernelGGL(kfn, grid, dim3(mm::NT), lds_, s, __VA_ARGS__);                        \
         };                                                                                            \
-        if (K.nper && K.need_r2) go(pr::KERN<T, 1, true>);                                            \
+        const bool mat_ = has_matern(K); /* (a Matern leaf sets need_r2) */                           \
+        if (K.nper && K.need_r2) mat_ ? go(pr::KERN##_m<T, 1, true>) : go(pr::KERN<T, 1, true>);      \
         else if (K.nper) go(pr::KERN<T, 1, false>);                                                   \
-        else go(pr::KERN<T, 0, true>);                                                                \
+        else mat_ ? go(pr::KERN##_m<T, 0, true>) : go(pr::KERN<T, 0, true>);                          \
     } while (0)
 
 // Lower triangle of K(X, X) + sigma2 I (identity beyond n) into A, from the features FU, FV
@@ -644,14 +723,15 @@ void launch_predict_mma(const KCanon<T>& K, const KCanon<T>* Kd, const T* FU, in
     GPRX_HIP(hipGetLastError());
 }
 
-// LML gradient trees: sum of Gaussian / GaussianExp / RQ / (one frequency) Periodic leaves
+// LML gradient trees: sum of Gaussian / GaussianExp / RQ / Matern / (one frequency) Periodic leaves
 template <typename T>
 bool pairs_grad_supported(const KCanon<T>& K) {
     if (!pairs_mma_supported<T>(K, 1) || !K.sum_leaves) return false;
     int nperleaf = 0;
     for (int l = 0; l < K.nleaf; l++) {
         const int ty = K.leaf[l].type;
-        if (ty != L_GAUSS && ty != L_GAUSS_EXP && ty != L_RQ && ty != L_PERIODIC) return false;
+        if (ty != L_GAUSS && ty != L_GAUSS_EXP && ty != L_RQ && ty != L_PERIODIC && ty != L_MATERN32 && ty != L_MATERN52)
+            return false;
         nperleaf += ty == L_PERIODIC;
     }
     return nperleaf <= 1;
@@ -684,9 +764,10 @@ void launch_lml_grad_mma(const KCanon<T>& K, const KCanon<T>* Kd, const T* X, in
         hipLaunchKernelGGL(kfn, grid, dim3(mm::NT), lds, s, Kd, FU, FV, (const T*)GU, (const T*)GV, nf, Kr, Kp, Kf,
                            T(0.5) * T(d), alpha, C, ldc, n, part, ctab, nf, n, alpha);
     };
-    if (K.nper && K.need_r2) go(pr::grad_mma_kernel<T, 1, true>);
+    const bool mat = has_matern(K);
+    if (K.nper && K.need_r2) mat ? go(pr::grad_mma_kernel_m<T, 1, true>) : go(pr::grad_mma_kernel<T, 1, true>);
     else if (K.nper) go(pr::grad_mma_kernel<T, 1, false>);
-    else go(pr::grad_mma_kernel<T, 0, true>);
+    else mat ? go(pr::grad_mma_kernel_m<T, 0, true>) : go(pr::grad_mma_kernel<T, 0, true>);
     hipLaunchKernelGGL(pr::grad_reduce_kernel, dim3(MAX_LEAF * 3), dim3(256), 0, s, (const double*)part, ntiles, acc);
     GPRX_HIP(hipGetLastError());
 }
@@ -721,9 +802,10 @@ void launch_lml_grad_mma_cross(const KCanon<T>& K, const KCanon<T>* Kd, const T*
         hipLaunchKernelGGL(kfn, dim3((unsigned)ntiles), dim3(mm::NT), lds, s, Kd, FU, FV, (const T*)GU, (const T*)GV,
                            nfu, Kr, Kp, Kf, T(0.5) * T(d), a, C, ldc, na, part, (const uint64_t*)nullptr, nfv, nb, b);
     };
-    if (K.nper && K.need_r2) go(pr::grad_mma_kernel<T, 1, true, true>);
+    const bool mat = has_matern(K);
+    if (K.nper && K.need_r2) mat ? go(pr::grad_mma_kernel_m<T, 1, true, true>) : go(pr::grad_mma_kernel<T, 1, true, true>);
     else if (K.nper) go(pr::grad_mma_kernel<T, 1, false, true>);
-    else go(pr::grad_mma_kernel<T, 0, true, true>);
+    else mat ? go(pr::grad_mma_kernel_m<T, 0, true, true>) : go(pr::grad_mma_kernel<T, 0, true, true>);
     hipLaunchKernelGGL(pr::grad_reduce_kernel, dim3(MAX_LEAF * 3), dim3(256), 0, s, (const double*)part, ntiles, acc);
     GPRX_HIP(hipGetLastError());
 }
@@ -744,7 +826,7 @@ TileBuild<T> pairs_tile_build(const KCanon<T>& K, const KCanon<T>* Kd, const T* 
     b.flag = flag;
     // as GPRX_PAIRS_DISPATCH.  0 (no fused build: the caller launches kbuild_mma_kernel) for
     // trees with products, which build_tile_sum does not separate, and for RationalQuadratic
-    // leaves: the fused path carries exp-form leaves only, to keep the factorisation kernel
+    // and Matern leaves: the fused path carries exp-form leaves only, to keep the factorisation kernel
     // small (its code and register budget are shared with every other task type)
     bool expform = K.sum_leaves != 0;
     for (int l = 0; l < K.nleaf; l++)

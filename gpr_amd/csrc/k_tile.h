@@ -150,7 +150,7 @@ __device__ inline void kernel_grad(const KCanon<T>& K, T r2, T s0, T s1, T f0, T
         }
         T g[3];
         leaf_grad(K.leaf[l], r2, s0, s1, f0, f1, g);
-        const int np = (K.leaf[l].type == L_WHITE) ? 1 : ((K.leaf[l].type == L_GAUSS || K.leaf[l].type == L_GAUSS_EXP) ? 2 : 3);
+        const int np = leaf_type_nparams(K.leaf[l].type);
         for (int q = 0; q < np; q++) out[K.param_base[l] + q] = adj * g[q];
     }
 }

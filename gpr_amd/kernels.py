@@ -16,9 +16,11 @@ OP = {
     "PeriodicKernel": 5,
     "SumKernel": 6,
     "ProductKernel": 7,
+    "Matern32Kernel": 8,
+    "Matern52Kernel": 9,
 }
 NPARAMS = {"GaussianKernel": 2, "GaussianExpKernel": 2, "WhiteKernel": 1, "RationalQuadraticKernel": 3,
-           "PeriodicKernel": 3}
+           "PeriodicKernel": 3, "Matern32Kernel": 2, "Matern52Kernel": 2}
 
 
 class KernelError(ValueError):
@@ -80,6 +82,16 @@ def Periodic(scale, b, sigma):
     return KernelNode("PeriodicKernel", [float(scale), float(b), float(sigma)])
 
 
+def Matern32(sigma, scale=1.0):
+    """k = scale^2 (1 + a) exp(-a), a = sqrt(3) r / |sigma| (not in the reference)."""
+    return KernelNode("Matern32Kernel", [float(sigma), float(scale)])
+
+
+def Matern52(sigma, scale=1.0):
+    """k = scale^2 (1 + a + a^2 / 3) exp(-a), a = sqrt(5) r / |sigma| (not in the reference)."""
+    return KernelNode("Matern52Kernel", [float(sigma), float(scale)])
+
+
 def Sum(k1, k2):
     return KernelNode("SumKernel", k1=k1, k2=k2)
 
@@ -127,11 +139,11 @@ def _parse(cur: _Cursor) -> KernelNode:
 
 def validate(node: KernelNode):
     """Constructor-time parameter checks (include/Kernel.h:529-530, 1003-1005)."""
-    if node.name == "GaussianKernel":
+    if node.name in ("GaussianKernel", "Matern32Kernel", "Matern52Kernel"):
         if node.params[0] == 0:
-            raise KernelError("GaussianKernel: sigma has to be positive")
+            raise KernelError(f"{node.name}: sigma has to be positive")
         if node.params[1] == 0:
-            raise KernelError("GaussianKernel: scale has to be positive")
+            raise KernelError(f"{node.name}: scale has to be positive")
     if node.name == "PeriodicKernel":
         if node.params[0] == 0:
             raise KernelError("PeriodicKernel: scale parameter has to be positive.")

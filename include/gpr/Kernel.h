@@ -4,7 +4,8 @@
 // reference (include/Kernel.h:40-1036): Kernel<T> with virtual operator()(x,y) and
 // GetDerivative(x,y); leaves GaussianKernel (sigma, scale), GaussianExpKernel (sigma,
 // scale), WhiteKernel (scale), RationalQuadraticKernel (scale, sigma, alpha),
-// PeriodicKernel (scale, b, sigma); composites SumKernel / ProductKernel.
+// PeriodicKernel (scale, b, sigma); composites SumKernel / ProductKernel.  Beyond the
+// reference: Matern32Kernel and Matern52Kernel (sigma, scale).
 //
 // operator() / GetDerivative evaluate ONE pair on the host (the reference's scalar API).
 // Matrix-shaped work never calls them: every kernel lowers itself with Describe() into the
@@ -363,6 +364,72 @@ private:
     T m_Scale, m_B, m_Sigma;
 };
 
+// Matern kernels, nu = 3/2 and 5/2 (not in the reference), parameters (sigma, scale) in the
+// order of GaussianKernel: with a = sqrt(NU2 r2) / |sigma| (NU2 = 2 nu = 3 or 5)
+//   3/2: k = s^2 (1 + a) e^-a,           dk/dsigma = s^2 a^2 e^-a / sigma
+//   5/2: k = s^2 (1 + a + a^2/3) e^-a,   dk/dsigma = s^2 (a^2/3) (1 + a) e^-a / sigma
+// and dk/ds = 2 k / s; finite at r = 0, no division by r.
+template <class T, int NU2>
+class MaternKernel : public Kernel<T> {
+    static_assert(NU2 == 3 || NU2 == 5, "MaternKernel: nu = 3/2 or 5/2");
+
+public:
+    typedef Kernel<T> Superclass;
+    typedef std::shared_ptr<MaternKernel> Pointer;
+    using typename Superclass::VectorType;
+    using typename Superclass::ParameterVectorType;
+    using typename Superclass::StringParameterVectorType;
+
+    MaternKernel(T sigma, T scale = 1) : m_Sigma(sigma), m_Scale(scale) { Assign({sigma, scale}); }
+    MaternKernel(const std::string& p1, const std::string& p2) : MaternKernel(this->S2P(p1), this->S2P(p2)) {}
+
+    T operator()(const VectorType& x, const VectorType& y) const override {
+        const T a = Arg(x, y);
+        return m_Scale * m_Scale * Poly(a) * std::exp(-a);
+    }
+    VectorType GetDerivative(const VectorType& x, const VectorType& y) const override {
+        const T a = Arg(x, y), e = std::exp(-a);
+        VectorType D(2);
+        D[0] = m_Scale * m_Scale * (NU2 == 3 ? a * a : a * a / 3 * (1 + a)) * e / m_Sigma;
+        D[1] = 2 * m_Scale * Poly(a) * e;
+        return D;
+    }
+    std::string ToString() const override { return Name() + "(" + this->ParametersToString(this->m_StringParameters) + ")"; }
+    unsigned GetNumberOfParameters() const override { return 2; }
+    void SetParameters(const ParameterVectorType& p) override {
+        if (p.size() != 2) throw std::string(Name() + "::SetParameters: wrong number of parameters.");
+        Assign(p);
+    }
+    static Pointer Load(const StringParameterVectorType& p) {
+        if (p.size() != 2) throw std::string(Name() + "::Load: wrong number of kernel parameters.");
+        return Pointer(new MaternKernel(Superclass::S2P(p[0]), Superclass::S2P(p[1])));
+    }
+    void Describe(std::vector<gprx_knode>& prog) const override {
+        this->push_leaf(prog, NU2 == 3 ? GPRX_K_MATERN32 : GPRX_K_MATERN52, this->m_Parameters);
+    }
+    static std::string Name() { return NU2 == 3 ? "Matern32Kernel" : "Matern52Kernel"; }
+
+private:
+    T Arg(const VectorType& x, const VectorType& y) const {
+        return std::sqrt(T(NU2) * this->dist2(x, y)) / std::fabs(m_Sigma);
+    }
+    static T Poly(T a) { return NU2 == 3 ? 1 + a : 1 + a + a * a / 3; }
+    void Assign(const ParameterVectorType& p) {  // (checked before the assignment, as GaussianKernel)
+        if (m_Sigma == 0) throw std::string(Name() + ": sigma has to be positive");
+        if (m_Scale == 0) throw std::string(Name() + ": scale has to be positive");
+        m_Sigma = p[0];
+        m_Scale = p[1];
+        this->m_Parameters = p;
+        this->m_StringParameters = {this->P2S(m_Sigma), this->P2S(m_Scale)};
+    }
+    T m_Sigma, m_Scale;
+};
+
+template <class T>
+using Matern32Kernel = MaternKernel<T, 3>;
+template <class T>
+using Matern52Kernel = MaternKernel<T, 5>;
+
 // ------------------------------------------------------------------------------------
 // Composites: gradient = [k1 params, k2 params]; Product multiplies by the other factor
 // (include/Kernel.h:165-178, 314-327).  The string parameters keep the reference layout
@@ -487,6 +554,8 @@ public:
         if (type == "PeriodicKernel") return PeriodicKernel<T>::Load(params);
         if (type == "RationalQuadraticKernel") return RationalQuadraticKernel<T>::Load(params);
         if (type == "WhiteKernel") return WhiteKernel<T>::Load(params);
+        if (type == "Matern32Kernel") return Matern32Kernel<T>::Load(params);
+        if (type == "Matern52Kernel") return Matern52Kernel<T>::Load(params);
         throw std::string("KernelFactory::GetKernel: failed to load kernel.");
     }
 };

@@ -63,6 +63,9 @@ typedef enum gprx_dtype { GPRX_F32 = 0, GPRX_F64 = 1 } gprx_dtype;
  *   WHITE             p = (scale)               include/Kernel.h:717-720
  *   RATIONAL_QUADRATIC p = (scale, sigma, alpha) include/Kernel.h:812-819
  *   PERIODIC          p = (scale, b, sigma)     include/Kernel.h:950-960
+ *   MATERN32          p = (sigma, scale)        s^2 (1 + a) e^-a, a = sqrt(3 r2) / |sigma|
+ *   MATERN52          p = (sigma, scale)        s^2 (1 + a + a^2/3) e^-a, a = sqrt(5 r2) / |sigma|
+ *                     (not in the reference; ops added within ABI version 2)
  *   SUM / PRODUCT     gradient = [k1 params, k2 params] include/Kernel.h:169-178, 318-327
  * The device evaluates a tree expanded into a sum of products of its leaves, within these
  * limits: at most 8 leaves, at most 16 product terms after the expansion (checked at every
@@ -79,7 +82,9 @@ typedef enum gprx_kop {
     GPRX_K_RATIONAL_QUADRATIC = 4,
     GPRX_K_PERIODIC = 5,
     GPRX_K_SUM = 6,
-    GPRX_K_PRODUCT = 7
+    GPRX_K_PRODUCT = 7,
+    GPRX_K_MATERN32 = 8,
+    GPRX_K_MATERN52 = 9
 } gprx_kop;
 
 #define GPRX_MAX_KNODES 32
