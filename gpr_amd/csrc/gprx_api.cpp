@@ -215,7 +215,12 @@ struct DevBuf {
         // GPRX_POISON (debugging): fresh buffers hold finite garbage (bytes 0x41: 12.1f, 2.3e6),
         // as reused memory does, so a read of unwritten memory shows in the results
         static const bool poison = std::getenv("GPRX_POISON") != nullptr;
-        if (poison) GPRX_HIP(hipMemset(p, 0x41, b));
+        // (the fill runs on the null stream, which the context's non-blocking streams do not wait
+        // for: drained here, or it can land after the first kernel's stores into the new buffer)
+        if (poison) {
+            GPRX_HIP(hipMemset(p, 0x41, b));
+            GPRX_HIP(hipDeviceSynchronize());
+        }
     }
     void release() {
         if (p) (void)hipFree(p);
@@ -867,6 +872,7 @@ static gprx_status model_fit(gprx_model* M, uint32_t flags, gprx_fit_info* out) 
     GPRX_REQUIRE(M->has_kernel, GPRX_ERR_STATE, "gprx: no kernel set");
     GPRX_HIP(hipSetDevice(ctx->device));
     M->trim_posterior_workspace();
+    M->sparse_cov = false;  // a dense fit's posterior covariance comes from its own factor, not a sparse GP's W
     hipStream_t s = ctx->stream;
     const KCanon<T>& K = kcanon<T>(M);
     // multi-GPU factorisation: an RCCL context with world > 1, a virtual-rank context, or
@@ -2636,6 +2642,7 @@ gprx_status gprx_model_set_kernel(gprx_model* M, const gprx_kernel_desc* k) {
     M->desc = *k;
     M->has_kernel = true;
     M->host_k = false;
+    M->sparse_cov = false;  // W belongs to the kernel it was computed with (set_sparse_cov comes after set_kernel)
     M->fitted = false;
     M->has_alpha = false;
     M->inv_ready = false;
@@ -2828,6 +2835,7 @@ gprx_status gprx_model_set_kernel_matrix(gprx_model* M, const void* K) {
     std::memset(&M->desc, 0, sizeof(M->desc));
     M->host_k = true;
     M->has_kernel = true;
+    M->sparse_cov = false;
     M->fitted = false;
     M->has_alpha = false;
     M->inv_ready = false;

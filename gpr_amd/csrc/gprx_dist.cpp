@@ -71,7 +71,10 @@ struct DMem {
         else GPRX_HIP(hipMalloc(&p, b));
         bytes = b;
         static const bool poison = std::getenv("GPRX_POISON") != nullptr;  // (debugging, as DevBuf)
-        if (poison) GPRX_HIP(hipMemset(p, 0x41, b));
+        if (poison) {  // (drained: the ranks' non-blocking streams do not wait for the null stream)
+            GPRX_HIP(hipMemset(p, 0x41, b));
+            GPRX_HIP(hipDeviceSynchronize());
+        }
     }
     void release() {
         if (p) (void)hipFree(p);

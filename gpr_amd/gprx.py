@@ -586,6 +586,8 @@ class Model:
             if not (isinstance(X, DeviceArray) and isinstance(Y, DeviceArray)) or X.dtype != self.dtype \
                     or Y.dtype != self.dtype:
                 raise TypeError("set_data: X and Y both DeviceArrays of the model's dtype, or both host arrays")
+            if self._host_kernel():
+                raise TypeError("set_data: the model's kernel has no device form and needs host arrays")
             n, d = X.shape
             m = Y.shape[1] if len(Y.shape) > 1 else 1
             self._c(lib().gprx_model_set_data(self.h, ctypes.c_void_p(X.p), ctypes.c_void_p(Y.p), n, d, m))
@@ -610,8 +612,11 @@ class Model:
         The latter is evaluated here on the host; the factorisation and solves stay on the
         device (gprx_model_set_kernel_matrix and the *_kx entry points)."""
         if callable(kernel) and not isinstance(kernel, str) and not hasattr(kernel, "op"):
+            if self._Xh is None and self.n:  # DeviceArray data: nothing on the host to evaluate it against
+                raise TypeError("set_kernel: a kernel with no device form needs host arrays in set_data "
+                                "(the model holds DeviceArrays)")
             self.kernel = kernel
-            if self._Xh is not None:  # else set_data evaluates it
+            if self._Xh is not None:  # else (no data yet) set_data evaluates it
                 self._set_host_kernel()
             return
         self.kernel = as_node(kernel)
