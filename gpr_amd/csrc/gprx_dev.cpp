@@ -8,7 +8,7 @@
 #include <vector>
 
 #include "../../include/gprx_dev.h"
-#include "gprx_internal.h"
+#include "gprx_model.h"
 #include "pt_sched.h"
 
 namespace gprx {
@@ -297,8 +297,7 @@ static gprx_status forward_panel_impl(const void* Lh, int64_t n, void* Rh, int r
 
 gprx_status gprx_dev_forward_panel_impl(gprx_dtype dtype, const void* L, int64_t n, void* R, int32_t rows,
                                         int32_t use_gemm, Exec* ex, hipStream_t s) {
-    return dtype == GPRX_F64 ? forward_panel_impl<double>(L, n, R, rows, use_gemm, *ex, s)
-                             : forward_panel_impl<float>(L, n, R, rows, use_gemm, *ex, s);
+    return by_dtype(dtype, [&](auto t) { return forward_panel_impl<decltype(t)>(L, n, R, rows, use_gemm, *ex, s); });
 }
 }  // namespace gprx
 
@@ -367,8 +366,7 @@ extern "C" int64_t gprx_dev_schedule_list(int32_t nc, int32_t nr, int32_t P, int
 namespace gprx {
 gprx_status gprx_dev_bench_impl(gprx_dtype dtype, int32_t what, int64_t M, int64_t N, int64_t K, int32_t iters,
                                 double* ms, Exec* ex) {
-    return dtype == GPRX_F64 ? bench_impl<double>(what, M, N, K, iters, ms, *ex)
-                             : bench_impl<float>(what, M, N, K, iters, ms, *ex);
+    return by_dtype(dtype, [&](auto t) { return bench_impl<decltype(t)>(what, M, N, K, iters, ms, *ex); });
 }
 }  // namespace gprx
 

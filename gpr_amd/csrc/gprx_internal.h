@@ -736,4 +736,28 @@ void launch_gather_rows(const double* X, const int64_t* idx, int64_t q, int d, d
 void launch_residual_scatter(const double* Y, const double* Kx, const double* a, double s2, const int64_t* idx,
                              int64_t q, int m, float* rhs, hipStream_t s);
 
+// ---- extra launchers (k_predict.hip, k_lml.hip) -----------------------------------------
+template <typename T>
+void launch_pair_kernel(const KCanon<T>& K, const T* Xa, const T* Xb, int64_t q, int d, T* out, hipStream_t s);
+template <typename T>
+void launch_rowdot(const T* Va, const T* Vb, int64_t ld, int64_t q, int64_t n, const T* kab, T* out, hipStream_t s);
+template <typename T>
+void trsm_rows(const T* A, int64_t ldA, int64_t np, const T* Linv, T* R, int64_t ld, int64_t qp, hipStream_t s);
+template <typename T>
+void launch_spd_inverse_from_factor(const T* A, int64_t ldA, int64_t np, const T* Linv, T* V, T* C, hipStream_t s);
+template <typename T>
+void launch_lml_grad(const KCanon<T>& K, const T* X, const T* tab, int64_t n, int d, const T* alpha, const T* C,
+                     int64_t ldc, double* acc /* MAX_LEAF*3 */, hipStream_t s);
+template <typename T>
+void launch_set_identity_pad(T* A, int64_t ld, int64_t n, int64_t np, hipStream_t s);
+template <typename T>
+void launch_gemm_add_lower(T* S, int64_t lds, const T* K, int64_t ldk, int64_t n, hipStream_t s);
+template <typename T>
+void launch_sym_fill(T* C, int64_t ldc, int64_t n, hipStream_t s);
+template <typename T>
+void launch_sum_partials(T* S, int64_t stride, int P, hipStream_t s);
+// (k_append.hip) S (lower tiles, n x n, lds) += the P split-K partials (n x n each), in order
+template <typename T>
+void launch_schur_sum(T* S, int64_t lds, const T* part, int64_t n, int P, hipStream_t s);
+
 }  // namespace gprx

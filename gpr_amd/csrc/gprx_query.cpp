@@ -1,0 +1,525 @@
+// gprx_query.cpp — what reads a fitted model: predict, the posterior covariance (dense, LU, sharded,
+// sparse), the core matrix, the log marginal likelihood and the caller-evaluated-kernel forms.
+#include "gprx_model.h"
+
+namespace gprx {
+
+template <typename T>
+gprx_status model_predict(gprx_model* M, const void* Xq, int64_t q, void* mean, void* deriv) {
+    GPRX_REQUIRE(M->has_alpha, GPRX_ERR_STATE, "GaussianProcess::ComputeKernelVectorInternal: gaussian process is not initialized.");
+    GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE, "gprx: a caller-evaluated kernel predicts through gprx_model_predict_kx");
+    hipStream_t s = M->ctx->stream;
+    const KCanon<T>& K = kcanon<T>(M);
+    const int d = M->d, m = M->m;
+    Points<T> Q;
+    DevBuf dmean, dder;
+    stage_points<T>(Q, K, Xq, q, d, M->ctx->device, s, false);
+    dmean.ensure(sizeof(T) * q * m);
+    if (!deriv && !env_predict_direct() && pairs_mma_supported<T>(K, m)) {
+        // mean only: MFMA pair statistics, K(Xq, X) never materialised (k_pairs.hip)
+        const int64_t qp = round_up(q, GT), npf = round_up(M->n, GT);
+        DevBuf fq;
+        train_features<T>(M, true, npf);
+        query_features<T>(M, Q.x, q, qp, fq);
+        launch_predict_mma<T>(K, M->kfit.put(K, s), fq.as<T>(), qp, M->featV.as<T>(), npf, d, M->alpha.as<T>(), M->n, m,
+                              q, dmean.as<T>(), s);
+        download(mean, dmean.p, sizeof(T) * q * m, s);
+        return GPRX_OK;
+    }
+    if (deriv) dder.ensure(sizeof(T) * q * d * m);
+    const int64_t ncz = (int64_t)m * (deriv ? (1 + d) : 1);
+    M->scratch1.ensure(sizeof(T) * M->n * ncz);
+    M->scratch2.ensure(sizeof(T) * q * ncz);
+    launch_predict<T>(K, M->X.as<T>(), M->tab.as<T>(), M->n, d, m, M->alpha.as<T>(), Q.x, Q.tab, q,
+                      dmean.as<T>(), deriv ? dder.as<T>() : nullptr, M->scratch1.as<T>(), M->scratch2.as<T>(), s);
+    download(mean, dmean.p, sizeof(T) * q * m, s);
+    if (deriv) download(deriv, dder.p, sizeof(T) * q * d * m, s);
+    return GPRX_OK;
+}
+
+// R = K(Xq, X) (qp x np, ld qp, zero padding), then R L^{-T} in place.  K(Xq, X) as MFMA pair
+// statistics (kcross_mma_kernel: the predict path's features of the queries and of the training
+// set) when the tree allows it -- 23 ms -> ~4 ms of the 300 ms variance leg at Q = 65536 against
+// the VALU kernel (GPRX_PREDICT=direct keeps that one).  fp64 only: the variance k(x,x) -
+// |L^{-1} k_x|^2 is a cancelling difference, and in fp32 the expanded |u|^2 + |v|^2 - 2 u.v
+// statistic loses ~eps (|x - c|/l)^2 per entry, which L^{-1} amplifies; fp32 models
+// keep the exact-difference VALU build.  feat_ready: the training features are already in
+// featV (the second side of a pair call).
+template <typename T>
+static void solve_rows_for(gprx_model* M, const T* dXq, const T* dtabQ, int64_t q, int64_t qp, T* R,
+                           bool feat_ready = false) {
+    hipStream_t s = M->ctx->stream;
+    const KCanon<T>& K = kcanon<T>(M);
+    const int64_t npf = round_up(M->n, GT);
+    const bool cross_mma =
+        std::is_same<T, double>::value && !env_predict_direct() && pairs_mma_supported<T>(K, 1) && npf <= M->np;
+    // R must be zero outside the q x n cross block (the solves run over qp x np); the MFMA cross
+    // build stores every entry of that block, so with no padding there is nothing to zero (the
+    // memset was 8.6 GB, 1.3 ms, per solve at Q = 65536, N = 16384)
+    if (!cross_mma || q != qp || M->n != M->np) GPRX_HIP(hipMemsetAsync(R, 0, sizeof(T) * qp * M->np, s));
+    if (cross_mma) {
+        if (!feat_ready) train_features<T>(M, true, npf);
+        query_features<T>(M, dXq, q, qp, M->pvFq);  // (model-owned: no hipMalloc + hipFree per call)
+        const KCanon<T>* kdev = M->kfit.put(K, s);
+        launch_kcross_mma<T>(K, kdev, M->pvFq.as<T>(), qp, q, M->featV.as<T>(), npf, M->n, M->d, R, qp,
+                             M->flag.as<int>(), s);
+    } else {
+        launch_kbuild<T>(K, dXq, dtabQ, q, M->X.as<T>(), M->tab.as<T>(), M->n, M->d, R, qp, 0, false, T(0),
+                         M->flag.as<int>(), s);
+    }
+    trsm_rows<T>(M->A.as<T>(), M->ld, M->np, M->Linv.as<T>(), R, qp, qp, s);
+}
+
+// operator()(x, y) / GetCredibleInterval (lib/GaussianProcess.cpp:84-114) on a SHARDED fit:
+// k(x, y) - (L^{-1} k_x) . (L^{-1} k_y) by the distributed forward substitution of the queries
+// (dist_posterior, k_dsolve.hip dist_pvar_kernel): the ranks keep their own rows of L, the
+// query columns V_k travel through the receive windows, the row sums are all-reduced.  Pairs
+// (x_p, y_p) with x != y ride in the same chunk (64 + 64 columns), variances 128 per chunk.
+template <typename T>
+static gprx_status model_posterior_cov_dist_core(gprx_model* M, const void* Xa, const void* Xb, int64_t q, bool same,
+                                                 void* out);
+
+// FNV-1a over bytes (the processes' query agreement below)
+static uint64_t fnv1a(const void* p, size_t n, uint64_t h = 1469598103934665603ull) {
+    const unsigned char* b = static_cast<const unsigned char*>(p);
+    for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull;
+    return h;
+}
+
+// On a multi-process context the sharded solve is a collective: every process runs the same
+// sequence of launches and exchanges.  The processes first agree on their arguments (q, whether
+// x == y, a hash of the queries).  Identical arguments (every process asks for the same pairs)
+// take the solve as they are; different ones -- e.g. each process its own query_shard slice,
+// q = 0 included -- are all-gathered, the solve runs once over every process's pairs, and each
+// process keeps its own.
+template <typename T>
+static gprx_status model_posterior_cov_dist(gprx_model* M, const void* Xa, const void* Xb, int64_t q, void* out) {
+    const int d = M->d;
+    const bool same = q == 0 || (Xa == Xb) || std::memcmp(Xa, Xb, sizeof(T) * q * d) == 0;
+    gprx_ctx* ctx = M->ctx;
+    if (!ctx->hc || ctx->world <= 1) return model_posterior_cov_dist_core<T>(M, Xa, Xb, q, same, out);
+    const int g = ctx->world;
+    struct Hdr {
+        int64_t q;
+        int64_t same;
+        uint64_t hash;
+    } h{q, same ? 1 : 0, fnv1a(Xa, sizeof(T) * q * d, fnv1a(same ? Xa : Xb, sizeof(T) * q * d))};
+    std::vector<Hdr> all(g);
+    ctx->hc->allgather(&h, sizeof(Hdr), all.data());
+    bool uniform = true;
+    int64_t qmax = 0, qtot = 0;
+    bool all_same = true;
+    for (const Hdr& x : all) {
+        uniform = uniform && x.q == h.q && x.same == h.same && x.hash == h.hash;
+        qmax = std::max(qmax, x.q);
+        qtot += x.q;
+        all_same = all_same && x.same;
+    }
+    if (uniform) return q ? model_posterior_cov_dist_core<T>(M, Xa, Xb, q, same, out) : GPRX_OK;
+    // every process's pairs, in rank order; this process's results from offset `off`
+    std::vector<T> mine((size_t)qmax * d * 2, T(0));
+    if (q) {
+        std::memcpy(mine.data(), Xa, sizeof(T) * q * d);
+        std::memcpy(mine.data() + (size_t)qmax * d, Xb, sizeof(T) * q * d);
+    }
+    std::vector<T> gath((size_t)qmax * d * 2 * g);
+    ctx->hc->allgather(mine.data(), sizeof(T) * mine.size(), gath.data());
+    std::vector<T> xa((size_t)std::max<int64_t>(qtot, 1) * d), xb((size_t)std::max<int64_t>(qtot, 1) * d);
+    int64_t off = 0, mine_off = 0;
+    for (int r = 0; r < g; r++) {
+        const T* src = gath.data() + (size_t)r * qmax * d * 2;
+        if (r == ctx->rank) mine_off = off;
+        std::memcpy(xa.data() + off * d, src, sizeof(T) * all[r].q * d);
+        std::memcpy(xb.data() + off * d, src + (size_t)qmax * d, sizeof(T) * all[r].q * d);
+        off += all[r].q;
+    }
+    if (qtot == 0) return GPRX_OK;
+    std::vector<T> res((size_t)qtot);
+    model_posterior_cov_dist_core<T>(M, xa.data(), all_same ? xa.data() : xb.data(), qtot, all_same, res.data());
+    if (q) std::memcpy(out, res.data() + mine_off, sizeof(T) * q);
+    return GPRX_OK;
+}
+
+template <typename T>
+static gprx_status model_posterior_cov_dist_core(gprx_model* M, const void* Xa, const void* Xb, int64_t q, bool same,
+                                                 void* out) {
+    hipStream_t s = M->ctx->stream;
+    const KCanon<T>& K = kcanon<T>(M);
+    const int d = M->d;
+    const int nchmax = dist_pvar_chunks(M->dist_engine);
+    const int per = same ? DB : DB / 2;  // pairs per chunk
+    const T* xa = static_cast<const T*>(Xa);
+    const T* xb = static_cast<const T*>(Xb);
+    DevBuf da, db, kab;
+    Points<T> Zc;  // one chunk's query columns
+    upload<T>(da, Xa, sizeof(T) * q * d, s);
+    upload<T>(db, Xb, sizeof(T) * q * d, s);
+    kab.ensure(sizeof(T) * q);
+    launch_pair_kernel<T>(K, da.as<T>(), db.as<T>(), q, d, kab.as<T>(), s);
+    std::vector<T> hk((size_t)q), res((size_t)q);
+    download(hk.data(), kab.p, sizeof(T) * q, s);
+    std::vector<double> sum;
+    for (int64_t p0 = 0; p0 < q;) {
+        const int64_t cnt = std::min<int64_t>(q - p0, (int64_t)nchmax * per);
+        const int nch = (int)((cnt + per - 1) / per);
+        const int64_t nq = (int64_t)nch * DB;
+        std::vector<T> Z((size_t)nq * d, T(0));
+        for (int64_t j = 0; j < cnt; j++) {
+            const int64_t c = j / per, jj = j % per;
+            std::memcpy(&Z[(size_t)(c * DB + jj) * d], xa + (p0 + j) * d, sizeof(T) * d);
+            if (!same) std::memcpy(&Z[(size_t)(c * DB + DB / 2 + jj) * d], xb + (p0 + j) * d, sizeof(T) * d);
+        }
+        stage_points<T>(Zc, K, Z.data(), nq, d, M->ctx->device, s, false);
+        dist_posterior<T>(M->dist_engine, K, M->X.as<T>(), K.nper > 0 ? M->tab.as<T>() : nullptr, M->n, d, Zc.x, Zc.tab,
+                          nch, !same, sum, s);
+        for (int64_t j = 0; j < cnt; j++) res[p0 + j] = (T)((double)hk[p0 + j] - sum[(j / per) * DB + j % per]);
+        p0 += cnt;
+    }
+    std::memcpy(out, res.data(), sizeof(T) * q);
+    return GPRX_OK;
+}
+
+template <typename T>
+gprx_status model_posterior_cov(gprx_model* M, const void* Xa, const void* Xb, int64_t q, void* out) {
+    GPRX_REQUIRE(M->fitted || M->sparse_cov, GPRX_ERR_STATE,
+                 "GaussianProcess::ComputeKernelVectorInternal: gaussian process is not initialized.");
+    GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE, "gprx: a caller-evaluated kernel uses gprx_model_posterior_cov_kx");
+    // a sharded fit solves the queries across the ranks (GPRX_DIST_POSTERIOR=dense: the dense
+    // factor gathered onto this process instead, as for the core matrix)
+    static const bool dense_forced = std::getenv("GPRX_DIST_POSTERIOR") &&
+                                     std::string(std::getenv("GPRX_DIST_POSTERIOR")) == "dense";
+    if (M->dist_fitted && !M->dist_dense && M->method == 0 && !dense_forced && dist_pvar_chunks(M->dist_engine) > 0)
+        return model_posterior_cov_dist<T>(M, Xa, Xb, q, out);
+    ensure_dense_factor<T>(M);  // (collective on a sharded fit's first dense use)
+    if (q == 0) return GPRX_OK;
+    hipStream_t s = M->ctx->stream;
+    const KCanon<T>& K = kcanon<T>(M);
+    const int d = M->d;
+    const int64_t qp = round_up(q, GT);
+    Points<T> Pa, Pb;
+    DevBuf Ra, Rb, kab, res;
+    stage_points<T>(Pa, K, Xa, q, d, M->ctx->device, s, false);
+    stage_points<T>(Pb, K, Xb, q, d, M->ctx->device, s, false);
+    if (M->sparse_cov) {  // k(x,y) - Kx^T W Ky over the inducing points, batched on the device
+        const int64_t Mp = round_up(M->n, GT);
+        DevBuf Z;
+        Ra.ensure(sizeof(T) * qp * Mp);
+        Rb.ensure(sizeof(T) * qp * Mp);
+        Z.ensure(sizeof(T) * qp * Mp);
+        GPRX_HIP(hipMemsetAsync(Ra.p, 0, sizeof(T) * qp * Mp, s));
+        GPRX_HIP(hipMemsetAsync(Rb.p, 0, sizeof(T) * qp * Mp, s));
+        launch_kbuild<T>(K, Pa.x, Pa.tab, q, M->X.as<T>(), M->tab.as<T>(), M->n, d, Ra.as<T>(), qp, 0, false,
+                         T(0), M->flag.as<int>(), s);
+        launch_kbuild<T>(K, Pb.x, Pb.tab, q, M->X.as<T>(), M->tab.as<T>(), M->n, d, Rb.as<T>(), qp, 0, false,
+                         T(0), M->flag.as<int>(), s);
+        launch_gemm_nt<T>(Z.as<T>(), qp, Rb.as<T>(), qp, M->sparseW.as<T>(), Mp, qp, Mp, Mp, T(1), T(0), false, s);
+        kab.ensure(sizeof(T) * q);
+        res.ensure(sizeof(T) * q);
+        launch_pair_kernel<T>(K, Pa.x, Pb.x, q, d, kab.as<T>(), s);
+        launch_rowdot<T>(Ra.as<T>(), Z.as<T>(), qp, q, Mp, kab.as<T>(), res.as<T>(), s);
+        download(out, res.p, sizeof(T) * q, s);
+        return GPRX_OK;
+    }
+    if (M->method == 1) {  // LU factors: k(x,y) - K(X,x)^T A^{-1} K(X,y), the reference's formula (:84-99)
+        const int64_t np = M->np;
+        DevBuf Kt, Wd, Kad;
+        Wd.ensure(sizeof(double) * np * q);
+        Kad.ensure(sizeof(double) * np * q);
+        auto cross = [&](const T* Xq, const T* tq, double* dst) {  // K(X, Xq): np x q column-major
+            T* buf;
+            if constexpr (std::is_same<T, double>::value) {
+                buf = dst;
+            } else {
+                Kt.ensure(sizeof(T) * np * q);
+                buf = Kt.as<T>();
+            }
+            GPRX_HIP(hipMemsetAsync(buf, 0, sizeof(T) * np * q, s));
+            launch_kbuild<T>(K, M->X.as<T>(), M->tab.as<T>(), M->n, Xq, tq, q, d, buf, np, 0, false, T(0),
+                             M->flag.as<int>(), s);
+            if constexpr (!std::is_same<T, double>::value) launch_convert<T, double>(buf, dst, np * q, s);
+        };
+        cross(Pb.x, Pb.tab, Wd.as<double>());
+        lu_solve_model(M, Wd.as<double>(), (int)q);
+        cross(Pa.x, Pa.tab, Kad.as<double>());
+        kab.ensure(sizeof(T) * q);
+        res.ensure(sizeof(T) * q);
+        launch_pair_kernel<T>(K, Pa.x, Pb.x, q, d, kab.as<T>(), s);
+        lu_coldot<T>(Kad.as<double>(), Wd.as<double>(), np, M->n, q, kab.as<T>(), res.as<T>(), s);
+        download(out, res.p, sizeof(T) * q, s);
+        return GPRX_OK;
+    }
+    // the variance (GetCredibleInterval, :102-114, pairs (x, x)): one solve, |L^{-1} k_x|^2
+    const bool same = (Xa == Xb) || std::memcmp(Xa, Xb, sizeof(T) * q * d) == 0;
+    kab.ensure(sizeof(T) * q);
+    res.ensure(sizeof(T) * q);
+    M->pvRa.ensure(sizeof(T) * qp * M->np);
+    if (!same) M->pvRb.ensure(sizeof(T) * qp * M->np);
+    {
+        // device time of the whole solve (stats class "posterior"): K(x, X), the forward
+        // solve (q np^2 flop) and the row dots
+        ProfScope ps_(KC_POSTERIOR, s, (same ? 1.0 : 2.0) * (double)q * (double)M->np * (double)M->np);
+        T* Ra_ = M->pvRa.as<T>();
+        solve_rows_for<T>(M, Pa.x, Pa.tab, q, qp, Ra_);
+        if (!same) solve_rows_for<T>(M, Pb.x, Pb.tab, q, qp, M->pvRb.as<T>(), true);
+        launch_pair_kernel<T>(K, Pa.x, Pb.x, q, d, kab.as<T>(), s);
+        launch_rowdot<T>(Ra_, same ? Ra_ : M->pvRb.as<T>(), qp, q, M->np, kab.as<T>(), res.as<T>(), s);
+    }
+    download(out, res.p, sizeof(T) * q, s);
+    return GPRX_OK;
+}
+
+// the explicit inverse from the LU factors (A^{-1} I, double, np x np column-major in luC)
+static void lu_inverse(gprx_model* M, DevBuf& luC) {
+    const int64_t np = M->np;
+    luC.ensure(sizeof(double) * np * np);
+    GPRX_HIP(hipMemsetAsync(luC.p, 0, sizeof(double) * np * np, M->ctx->stream));
+    launch_set_identity_pad<double>(luC.as<double>(), np, 0, np, M->ctx->stream);
+    lu_solve_model(M, luC.as<double>(), (int)np);
+}
+
+template <typename T>
+gprx_status model_core_matrix(gprx_model* M, void* Cout) {
+    GPRX_REQUIRE(M->fitted, GPRX_ERR_STATE, "gprx: model is not fitted");
+    ensure_dense_factor<T>(M);
+    hipStream_t s = M->ctx->stream;
+    if (M->method == 1) {  // dgetri_'s inverse (include/LAPACKUtils.h:49) from the LU factors
+        DevBuf luC;
+        lu_inverse(M, luC);
+        const int64_t n = M->n, np = M->np;
+        std::vector<double> h((size_t)n * n);
+        GPRX_HIP(hipStreamSynchronize(s));
+        GPRX_HIP(hipGetLastError());
+        GPRX_HIP(hipMemcpy2D(h.data(), sizeof(double) * n, luC.p, sizeof(double) * np, sizeof(double) * n, n,
+                             hipMemcpyDeviceToHost));
+        T* C = reinterpret_cast<T*>(Cout);
+        for (int64_t j = 0; j < n; j++)
+            for (int64_t i = 0; i < n; i++) C[(size_t)i * n + j] = (T)h[(size_t)j * n + i];
+        return GPRX_OK;
+    }
+    model_inverse<T>(M);
+    const int64_t n = M->n, np = M->np;
+    std::vector<T> h((size_t)n * n);
+    // column j of C (lower part rows >= j) -> row-major; C symmetric
+    GPRX_HIP(hipStreamSynchronize(s));
+    GPRX_HIP(hipGetLastError());
+    GPRX_HIP(hipMemcpy2D(h.data(), sizeof(T) * n, M->C.p, sizeof(T) * np, sizeof(T) * n, n, hipMemcpyDeviceToHost));
+    mirror_lower<T>(h.data(), n, n, reinterpret_cast<T*>(Cout));  // h[j*n + i] = C(i, j) valid for i >= j
+    return GPRX_OK;
+}
+
+// C = the LU factors' inverse in the model's T (the reference casts back), for the gradients
+template <typename T>
+static void lu_inverse_to_C(gprx_model* M) {
+    hipStream_t s = M->ctx->stream;
+    const int64_t np = M->np;
+    DevBuf luC;
+    lu_inverse(M, luC);
+    M->C.ensure(sizeof(T) * np * np);
+    if constexpr (std::is_same<T, double>::value)
+        GPRX_HIP(hipMemcpyAsync(M->C.p, luC.p, sizeof(double) * np * np, hipMemcpyDeviceToDevice, s));
+    else
+        launch_convert<double, T>(luC.as<double>(), M->C.as<T>(), np * np, s);
+    GPRX_HIP(hipStreamSynchronize(s));
+}
+
+template <typename T>
+gprx_status model_lml(gprx_model* M, uint32_t flags, double* value, double* grad, int32_t* nparams,
+                      double* logdet) {
+    GPRX_REQUIRE(M->m == 1, GPRX_ERR_DIM,
+                 "GaussianLogLikelihood: only one output dimension is supported (the reference's data-fit term is "
+                 "m x m, include/Likelihood.h:175)");
+    GPRX_REQUIRE(!(M->host_k && grad && (flags & GPRX_LML_GRAD)), GPRX_ERR_STATE,
+                 "gprx: a caller-evaluated kernel takes its derivative matrices through gprx_model_lml_dk");
+    gprx_fit_info fi;
+    M->want_inv = grad && (flags & GPRX_LML_GRAD);
+    gprx_status st;
+    try {
+        // the likelihood inverts with the GP's method too (include/Likelihood.h:77-79 ->
+        // ComputeCoreMatrixWithDeterminant): a matrix the Cholesky rejects takes the LU
+        // the value and gradient come from the factor (and its inverse), never from alpha:
+        // an fp32 model's fp64 refinement of alpha would be thrown away (GPRX_FIT_F32_NO_REFINE)
+        st = model_fit<T>(M,
+                          ((flags & GPRX_LML_DISTRIBUTED) ? GPRX_FIT_DISTRIBUTED : 0u) |
+                              ((flags & GPRX_LML_FORCE_LU) ? GPRX_FIT_FORCE_LU : 0u) | GPRX_FIT_F32_NO_REFINE,
+                          &fi);
+    } catch (...) {
+        M->want_inv = false;
+        throw;
+    }
+    M->want_inv = false;
+    if (st != GPRX_OK) return st;
+    const KCanon<T>& K = kcanon<T>(M);
+    const double n = (double)M->n;
+    const T df = (T)(-0.5 * fi.datafit);
+    const T ct = (T)(-n / 2.0 * std::log(2 * M_PI));  // include/Likelihood.h:192
+    double v;
+    // LU fits can have det <= 0: the reference's clamp (:180-188) applies in both modes
+    const double det_sign = (M->method == 1) ? M->lu_sign : 1.0;
+    if ((flags & GPRX_LML_COMPAT) || det_sign <= 0) {
+        // include/Likelihood.h:77-79 narrows the long-double determinant to T, :180-188 clamps
+        typedef long double HP;
+        const HP det_ld = (HP)det_sign * std::exp((HP)fi.logdet);
+        const HP det = (HP)(T)det_ld;
+        HP cp;
+        if (det <= std::numeric_limits<HP>::min()) cp = -0.5L * std::log(std::numeric_limits<HP>::min());
+        else if (det > std::numeric_limits<HP>::max()) cp = -0.5L * std::log(std::numeric_limits<HP>::max());
+        else cp = -0.5L * std::log(det);
+        v = (double)(T)(df + (T)(cp + ct));
+    } else {
+        v = (double)df - 0.5 * fi.logdet + (double)ct;
+    }
+    if (std::isinf(v))
+        throw Error{GPRX_ERR_NONFINITE, "GaussianLogLikelihood::GetValueAndParameterDerivatives: likelihood is infinite."};
+    if (value) *value = v;
+    if (logdet) *logdet = fi.logdet;
+    if (nparams) *nparams = K.nparams;
+    if (grad && (flags & GPRX_LML_GRAD)) {
+        hipStream_t s = M->ctx->stream;
+        if (M->method == 1) {
+            lu_inverse_to_C<T>(M);
+        } else if (!M->inv_ready || (M->dist_fitted && !M->dist_inv_tiles && !M->dist_dense)) {
+            ensure_dense_factor<T>(M);
+            model_inverse<T>(M);
+        }
+        M->grad.ensure(sizeof(double) * MAX_LEAF * 3);
+        GPRX_HIP(hipMemsetAsync(M->grad.p, 0, sizeof(double) * MAX_LEAF * 3, s));
+        static const bool direct_grad =
+            std::getenv("GPRX_LML_GRAD") && std::string(std::getenv("GPRX_LML_GRAD")) == "direct";
+        const int64_t np = M->np, npf = round_up(M->n, GT);
+        if (!direct_grad && npf == np && pairs_grad_supported<T>(K)) {
+            // pair statistics (and the periodic b-derivative statistic) on the MFMA units
+            const int64_t kg = pairs_grad_feature_cols<T>(K, M->d);
+            train_features<T>(M, false, np);
+            train_features<T>(M, true, np);
+            const KCanon<T>* kdev = M->kfit.put(K, s);
+            M->scratch1.ensure(sizeof(T) * np * std::max<int64_t>(kg, 1));
+            M->scratch2.ensure(sizeof(T) * np * std::max<int64_t>(kg, 1));
+            const int64_t nt = np / GT;
+            M->pack.ensure(sizeof(double) * MAX_LEAF * 3 * nt * (nt + 1) / 2);
+            if (M->dist_fitted && M->dist_inv_tiles) {
+                // sharded fit in LML mode: each rank sums (alpha alpha^T - C) o dK/dp over the
+                // lower tiles of its own row blocks, C straight from its packed C tiles (the
+                // sharded potri riding along in the factorisation); one reduction over the ranks
+                dist_lml_grad<T>(M->dist_engine, K, kdev, M->X.as<T>(), M->n, M->d,
+                                 M->featU.as<T>(), M->featV.as<T>(), M->scratch1.as<T>(), M->scratch2.as<T>(), np,
+                                 M->alpha.as<T>(), M->pack.as<double>(), M->grad.as<double>(), s);
+            } else {
+                launch_lml_grad_mma<T>(K, kdev, M->X.as<T>(), M->n, M->d, M->featU.as<T>(),
+                                       M->featV.as<T>(), M->scratch1.as<T>(), M->scratch2.as<T>(), np,
+                                       M->alpha.as<T>(), M->C.as<T>(), M->np, M->pack.as<double>(),
+                                       M->grad.as<double>(), s);
+            }
+        } else {
+            launch_lml_grad<T>(K, M->X.as<T>(), M->tab.as<T>(), M->n, M->d, M->alpha.as<T>(), M->C.as<T>(), M->np,
+                               M->grad.as<double>(), s);
+        }
+        double acc[MAX_LEAF * 3];
+        download(acc, M->grad.p, sizeof(acc), s);
+        for (int l = 0; l < K.nleaf; l++) {
+            const int t = K.leaf[l].type;
+            const int np = leaf_type_nparams(t);
+            for (int q = 0; q < np; q++) grad[K.param_base[l] + q] = 0.5 * acc[l * 3 + q];
+        }
+    }
+    return GPRX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// caller-evaluated kernels (k_hostk.hip): predict, posterior covariance and the LML gradient
+// from the caller's kernel vectors / derivative matrices
+// ---------------------------------------------------------------------------------------
+template <typename T>
+gprx_status model_predict_kx(gprx_model* M, const void* Kx, const void* Xq, int64_t q, void* mean, void* deriv) {
+    GPRX_REQUIRE(M->has_alpha, GPRX_ERR_STATE, "GaussianProcess::ComputeKernelVectorInternal: gaussian process is not initialized.");
+    GPRX_REQUIRE(!deriv || Xq, GPRX_ERR_ARG, "gprx_model_predict_kx: the derivative needs the query points");
+    hipStream_t s = M->ctx->stream;
+    const int d = M->d, m = M->m;
+    const int64_t n = M->n;
+    DevBuf dk, dq, dmean, dder;
+    upload<T>(dk, Kx, sizeof(T) * q * n, s);
+    if (deriv) {
+        upload<T>(dq, Xq, sizeof(T) * q * d, s);
+        dder.ensure(sizeof(T) * q * d * m);
+    }
+    dmean.ensure(sizeof(T) * q * m);
+    launch_kx_predict<T>(dk.as<T>(), deriv ? dq.as<T>() : nullptr, M->X.as<T>(), q, n, d, M->alpha.as<T>(), m,
+                         dmean.as<T>(), deriv ? dder.as<T>() : nullptr, s);
+    download(mean, dmean.p, sizeof(T) * q * m, s);
+    if (deriv) download(deriv, dder.p, sizeof(T) * q * d * m, s);
+    return GPRX_OK;
+}
+
+template <typename T>
+gprx_status model_posterior_cov_kx(gprx_model* M, const void* Kxa, const void* Kxb, const void* kab, int64_t q,
+                                   void* out) {
+    GPRX_REQUIRE(M->fitted, GPRX_ERR_STATE, "GaussianProcess::ComputeKernelVectorInternal: gaussian process is not initialized.");
+    GPRX_REQUIRE(!M->dist_fitted, GPRX_ERR_STATE, "gprx: the posterior covariance needs a single-GPU fit");
+    hipStream_t s = M->ctx->stream;
+    const int64_t n = M->n, np = M->np, qp = round_up(q, GT);
+    DevBuf dkab, res;
+    upload<T>(dkab, kab, sizeof(T) * q, s);
+    res.ensure(sizeof(T) * q);
+    const T* ka = reinterpret_cast<const T*>(Kxa);
+    const T* kb = reinterpret_cast<const T*>(Kxb);
+    if (M->method == 1) {  // LU: k(x,y) - K(X,x)^T A^{-1} K(X,y) (lib/GaussianProcess.cpp:84-99)
+        std::vector<double> ha((size_t)np * q, 0.0), hb((size_t)np * q, 0.0);  // np x q column-major
+        for (int64_t j = 0; j < q; j++)
+            for (int64_t i = 0; i < n; i++) {
+                ha[(size_t)j * np + i] = (double)ka[j * n + i];
+                hb[(size_t)j * np + i] = (double)kb[j * n + i];
+            }
+        DevBuf Wd, Kad;
+        upload<double>(Wd, hb.data(), sizeof(double) * np * q, s);
+        upload<double>(Kad, ha.data(), sizeof(double) * np * q, s);
+        lu_solve_model(M, Wd.as<double>(), (int)q);
+        lu_coldot<T>(Kad.as<double>(), Wd.as<double>(), np, n, q, dkab.as<T>(), res.as<T>(), s);
+    } else {  // Cholesky: k(x,y) - (L^{-1} kx) . (L^{-1} ky), rows qp x np (ld qp)
+        std::vector<T> ha((size_t)qp * np, T(0)), hb((size_t)qp * np, T(0));
+        for (int64_t j = 0; j < q; j++)
+            for (int64_t i = 0; i < n; i++) {
+                ha[(size_t)i * qp + j] = ka[j * n + i];
+                hb[(size_t)i * qp + j] = kb[j * n + i];
+            }
+        DevBuf Ra, Rb;
+        upload<T>(Ra, ha.data(), sizeof(T) * qp * np, s);
+        upload<T>(Rb, hb.data(), sizeof(T) * qp * np, s);
+        trsm_rows<T>(M->A.as<T>(), M->ld, np, M->Linv.as<T>(), Ra.as<T>(), qp, qp, s);
+        trsm_rows<T>(M->A.as<T>(), M->ld, np, M->Linv.as<T>(), Rb.as<T>(), qp, qp, s);
+        launch_rowdot<T>(Ra.as<T>(), Rb.as<T>(), qp, q, np, dkab.as<T>(), res.as<T>(), s);
+    }
+    download(out, res.p, sizeof(T) * q, s);
+    return GPRX_OK;
+}
+
+template <typename T>
+gprx_status model_lml_dk(gprx_model* M, uint32_t flags, const void* dK, int32_t P, double* value, double* grad,
+                         double* logdet) {
+    GPRX_REQUIRE(P >= 0 && (P == 0 || dK), GPRX_ERR_ARG, "gprx_model_lml_dk: bad derivative matrices");
+    gprx_status st = model_lml<T>(M, flags & ~GPRX_LML_GRAD, value, nullptr, nullptr, logdet);
+    if (st != GPRX_OK || !grad || P == 0) return st;
+    hipStream_t s = M->ctx->stream;
+    const int64_t n = M->n, np = M->np;
+    if (M->method == 1) lu_inverse_to_C<T>(M);
+    else model_inverse<T>(M);
+    DevBuf ddk, g;
+    upload<T>(ddk, dK, sizeof(T) * (size_t)P * n * n, s);
+    g.ensure(sizeof(double) * P);
+    launch_dk_grad<T>(ddk.as<T>(), P, n, M->alpha.as<T>(), M->C.as<T>(), np, g.as<double>(), s);
+    download(grad, g.p, sizeof(double) * P, s);
+    return GPRX_OK;
+}
+
+#define GPRX_INST(T)                                                                                      \
+    template gprx_status model_predict<T>(gprx_model*, const void*, int64_t, void*, void*);                \
+    template gprx_status model_posterior_cov<T>(gprx_model*, const void*, const void*, int64_t, void*);    \
+    template gprx_status model_core_matrix<T>(gprx_model*, void*);                                         \
+    template gprx_status model_lml<T>(gprx_model*, uint32_t, double*, double*, int32_t*, double*);         \
+    template gprx_status model_predict_kx<T>(gprx_model*, const void*, const void*, int64_t, void*, void*); \
+    template gprx_status model_posterior_cov_kx<T>(gprx_model*, const void*, const void*, const void*,     \
+                                                   int64_t, void*);                                        \
+    template gprx_status model_lml_dk<T>(gprx_model*, uint32_t, const void*, int32_t, double*, double*, double*);
+GPRX_INST(float)
+GPRX_INST(double)
+#undef GPRX_INST
+
+}  // namespace gprx

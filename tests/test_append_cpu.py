@@ -1,5 +1,5 @@
 """gprx_model_append without a GPU: the ABI additions, and the block-boundary algebra the device
-code follows (gprx_api.cpp model_append), restated in numpy against the oracle.
+code follows (gprx_fit.cpp model_append), restated in numpy against the oracle.
 
 With n samples fitted, k new ones, n0 = floor(n / 128) * 128 and t = n - n0:
   * rows [0, n0) of L do not depend on later rows and are kept;

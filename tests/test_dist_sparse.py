@@ -1,4 +1,4 @@
-"""World-size-2 gloo restatement of the row-sharded sparse fit (gprx_api.cpp sparse_fit_impl
+"""World-size-2 gloo restatement of the row-sharded sparse fit (gprx_sparse.cpp sparse_fit_impl
 on an RCCL context, SURVEY.md 8(e) "Sparse fit: shard N rows; per GPU accumulate Knm^T Knm
 and Knm^T Y; all-reduce"): each rank forms sigma^-2 [Kmn; Y^T][Kmn; Y^T]^T over its own dense
 rows, one all-reduce sums them, and every rank solves S = Kmm + jitter I + sum for RV and
@@ -67,7 +67,7 @@ def test_row_sharded_sparse_world2(tmp_path):
 
 
 def _lml_worker(rank, world, port, n, d, M, out):
-    """Row-sharded sparse likelihood (gprx_api.cpp sparse_lml_impl on an RCCL context): the
+    """Row-sharded sparse likelihood (gprx_sparse.cpp sparse_lml_impl on an RCCL context): the
     normal equations all-reduced as in the fit, then each rank's data terms (y^T y, N) and its
     rows' gradient partials sum_{i in rank} sum_a Omega_ia dk(x_i, xm_a)/dp all-reduced once;
     the M x M part (replicated) is added after the reduction."""

@@ -278,7 +278,7 @@ def test_sparse_reference_gradient_config(ctx):
 
 def test_sparse_streamed_block_reuse(monkeypatch):
     """The streamed Kmn block lives in the context between fits and only the columns a longer
-    chunk left behind are re-zeroed (gprx_api.cpp SparseNE::dA_zero): fits of different lengths
+    chunk left behind are re-zeroed (gprx_sparse.cpp SparseNE::dA_zero): fits of different lengths
     (a ragged last chunk, then whole chunks, then ragged again) on one context give the same bits
     as the same fits on fresh contexts."""
     import gpr_amd

@@ -2,7 +2,7 @@
 restatement of SparseGaussianLogLikelihood::GetValueAndParameterDerivatives
 (include/SparseLikelihood.h:231-344: N x N C_inv by EfficientInversion, the A_p stack, the
 long-double EfficientDeterminant with its clamps).  The device evaluates the same quantities
-in O(N M^2) (Woodbury; gprx_api.cpp sparse_lml_impl).  Sparse-path parity is unpinned by the
+in O(N M^2) (Woodbury; gprx_sparse.cpp sparse_lml_impl).  Sparse-path parity is unpinned by the
 reference's own tests (tests/SparseInferenceTest.cpp:486-489 are disabled): the oracle is the
 checker, cross-checked against numpy in tests/test_oracle_numpy.py.
 

@@ -1,6 +1,6 @@
 """Kernel trees at the limits of the device form, against the CPU oracle in fp64.
 
-canonicalize (gprx_api.cpp) lowers a tree to at most MAX_LEAF = 8 leaves, MAX_TERM = 16 product
+canonicalize (gprx_canon.cpp) lowers a tree to at most MAX_LEAF = 8 leaves, MAX_TERM = 16 product
 terms and MAX_PER = 2 periodic leaves, each periodic leaf with a sin/cos table slot of its own.
 A tree with two periodic leaves is off the MFMA pair-statistics paths (pairs_mma_supported), so
 every entry point runs the direct kernels' NPER = 2 instantiations: sincos_tables_kernel's second
