@@ -230,6 +230,29 @@ gprx_status gprx_model_append(gprx_model* M, const void* Xnew, const void* Ynew,
         });
 }
 
+gprx_status gprx_model_remove(gprx_model* M, int64_t first, int64_t count, uint32_t flags, gprx_fit_info* info) {
+    return model_call(
+        M, true, "gprx_model_remove: NULL model", CALL_PROF,
+        [&] {
+            GPRX_REQUIRE(!((M->ctx->hc && M->ctx->world > 1) || M->ctx->virt), GPRX_ERR_STATE,
+                         "gprx_model_remove: sharded contexts (multi-rank or virtual-rank) refit in full: use "
+                         "gprx_model_set_data and gprx_model_fit");
+            return false;
+        },
+        [&] {
+            GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE,
+                         "gprx_model_remove: a caller-evaluated kernel matrix would have to be reduced by the caller");
+            GPRX_REQUIRE(!M->sparse_cov, GPRX_ERR_STATE, "gprx_model_remove: a sparse-covariance model holds no factor");
+            GPRX_REQUIRE(M->fitted && M->has_data && M->has_kernel, GPRX_ERR_STATE,
+                         "gprx_model_remove: gaussian process is not initialized.");
+            GPRX_REQUIRE(!M->dist_fitted, GPRX_ERR_STATE, "gprx_model_remove: the model was fitted sharded");
+            GPRX_REQUIRE(first >= 0 && count >= 1 && first <= M->n - count, GPRX_ERR_DIM,
+                         "gprx_model_remove: the samples [first, first + count) must lie inside the model's");
+            GPRX_REQUIRE(count < M->n, GPRX_ERR_DIM, "gprx_model_remove: no sample would be left");
+            return by_dtype(M->dt, [&](auto t) { return model_remove<decltype(t)>(M, first, count, flags, info); });
+        });
+}
+
 gprx_status gprx_model_get_alpha(gprx_model* M, void* alpha) {
     return model_call(M, alpha, "gprx_model_get_alpha: NULL argument", 0, [&] {
         GPRX_REQUIRE(M->has_alpha, GPRX_ERR_STATE, "gprx: model is not fitted");
@@ -519,6 +542,19 @@ gprx_status gprx_dev_forward_panel(gprx_ctx* ctx, gprx_dtype dtype, const void* 
     return gprx_dev_forward_panel_impl(dtype, L, n, R, rows, use_gemm, &ctx->ex, ctx->stream);
     API_END(ctx)
 }
+
+gprx_status gprx_dev_factor_update(gprx_ctx* ctx, gprx_dtype dtype, const void* L, int64_t n, const void* X, int32_t r,
+                                   void* Lout, void* LinvOut) {
+    API_BEGIN
+    GPRX_REQUIRE(ctx, GPRX_ERR_ARG, "gprx_dev_factor_update: NULL context");
+    GPRX_REQUIRE(dtype == GPRX_F32 || dtype == GPRX_F64, GPRX_ERR_ARG, "gprx_dev_factor_update: bad dtype");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPRX_HIP(hipSetDevice(ctx->device));
+    return gprx_dev_factor_update_impl(dtype, L, n, X, r, Lout, LinvOut, &ctx->ex, ctx->stream);
+    API_END(ctx)
+}
+
+int32_t gprx_dev_factor_update_width(void) { return factor_update_width(); }
 
 gprx_status gprx_dev_build_matrix(gprx_ctx* ctx, gprx_dtype dt, const gprx_kernel_desc* k, const void* X, int64_t n,
                                   int32_t d, double sigma, int32_t path, void* K) {

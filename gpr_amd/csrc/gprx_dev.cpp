@@ -299,6 +299,78 @@ gprx_status gprx_dev_forward_panel_impl(gprx_dtype dtype, const void* L, int64_t
                                         int32_t use_gemm, Exec* ex, hipStream_t s) {
     return by_dtype(dtype, [&](auto t) { return forward_panel_impl<decltype(t)>(L, n, R, rows, use_gemm, *ex, s); });
 }
+
+// gprx_dev_factor_update: the rotation kernel (k_remove.hip) alone on a host factor: every block
+// from 0 on, nothing shifted.  Lout is the new lower factor (row-major, zeros above the diagonal),
+// LinvOut the inverse of each of its diagonal blocks (n x 128, row-major: block b in rows
+// [128 b, 128 b + 128)).  The output buffers start from a fixed bit pattern, so what the kernel
+// does not write shows.
+template <typename T>
+static gprx_status factor_update_impl(const void* Lh, int64_t n, const void* Xh, int r, void* Lout, void* LinvOut,
+                                      Exec& ex, hipStream_t s) {
+    GPRX_REQUIRE(Lh && Xh && Lout && LinvOut && n > 0 && n % DB == 0 && r >= 1, GPRX_ERR_ARG,
+                 "gprx_dev_factor_update: n must be a positive multiple of 128 and r >= 1");
+    const T* L = static_cast<const T*>(Lh);
+    const T* X = static_cast<const T*>(Xh);
+    const int nb = (int)(n / DB);
+    T guard;
+    std::memset(&guard, 0x5a, sizeof(T));
+    std::vector<T> hA((size_t)n * n, guard), hX((size_t)n * r), hO((size_t)n * n, guard), hLi((size_t)n * DB, guard);
+    for (int64_t i = 0; i < n; i++) {
+        for (int64_t j = 0; j <= i; j++) hA[(size_t)i + (size_t)j * n] = L[(size_t)i * n + j];
+        for (int64_t v = 0; v < r; v++) hX[(size_t)i + (size_t)v * n] = X[(size_t)i * r + v];
+    }
+    T *dA = nullptr, *dX = nullptr, *dO = nullptr, *dLi = nullptr, *dW = nullptr;
+    int* dinfo = nullptr;
+    gprx_status st = GPRX_OK;
+    std::string msg;
+    try {
+        GPRX_HIP(hipMalloc(&dA, sizeof(T) * hA.size()));
+        GPRX_HIP(hipMalloc(&dX, sizeof(T) * hX.size()));
+        GPRX_HIP(hipMalloc(&dO, sizeof(T) * hO.size()));
+        GPRX_HIP(hipMalloc(&dLi, sizeof(T) * hLi.size()));
+        GPRX_HIP(hipMalloc(&dW, sizeof(T) * factor_update_ws_elems(nb, r)));
+        GPRX_HIP(hipMalloc(&dinfo, sizeof(int)));
+        GPRX_HIP(hipStreamSynchronize(s));
+        GPRX_HIP(hipMemcpy(dA, hA.data(), sizeof(T) * hA.size(), hipMemcpyHostToDevice));
+        GPRX_HIP(hipMemcpy(dX, hX.data(), sizeof(T) * hX.size(), hipMemcpyHostToDevice));
+        GPRX_HIP(hipMemcpy(dO, hO.data(), sizeof(T) * hO.size(), hipMemcpyHostToDevice));
+        GPRX_HIP(hipMemcpy(dLi, hLi.data(), sizeof(T) * hLi.size(), hipMemcpyHostToDevice));
+        const int big = INT_MAX;
+        GPRX_HIP(hipMemcpy(dinfo, &big, sizeof(int), hipMemcpyHostToDevice));
+        launch_factor_update<T>(dA, n, dO, n, dLi, dX, n, r, 0, 0, n, 0, nb, dW, dinfo, ex, s);
+        GPRX_HIP(hipStreamSynchronize(s));
+        GPRX_HIP(hipGetLastError());
+        int hinfo = 0;
+        GPRX_HIP(hipMemcpy(&hinfo, dinfo, sizeof(int), hipMemcpyDeviceToHost));
+        GPRX_HIP(hipMemcpy(hO.data(), dO, sizeof(T) * hO.size(), hipMemcpyDeviceToHost));
+        GPRX_HIP(hipMemcpy(hLi.data(), dLi, sizeof(T) * hLi.size(), hipMemcpyDeviceToHost));
+        GPRX_REQUIRE(hinfo >= 0, GPRX_ERR_HIP, "gprx_dev_factor_update: a chained wait timed out");
+        T* Lo = static_cast<T*>(Lout);
+        T* Lio = static_cast<T*>(LinvOut);
+        for (int64_t i = 0; i < n; i++) {
+            // (tiles above the diagonal are not the kernel's to write: zero in the row-major result)
+            for (int64_t j = 0; j < n; j++) Lo[(size_t)i * n + j] = j / DB <= i / DB ? hO[(size_t)i + (size_t)j * n] : T(0);
+            for (int64_t c = 0; c < DB; c++) Lio[(size_t)i * DB + c] = hLi[(size_t)(i / DB) * DB * DB + i % DB + (size_t)c * DB];
+        }
+    } catch (const Error& e) {
+        st = e.st;
+        msg = e.msg;
+    }
+    (void)hipFree(dA);
+    (void)hipFree(dX);
+    (void)hipFree(dO);
+    (void)hipFree(dLi);
+    (void)hipFree(dW);
+    (void)hipFree(dinfo);
+    if (st != GPRX_OK) throw Error{st, msg};
+    return GPRX_OK;
+}
+
+gprx_status gprx_dev_factor_update_impl(gprx_dtype dtype, const void* L, int64_t n, const void* X, int32_t r,
+                                        void* Lout, void* LinvOut, Exec* ex, hipStream_t s) {
+    return by_dtype(dtype, [&](auto t) { return factor_update_impl<decltype(t)>(L, n, X, r, Lout, LinvOut, *ex, s); });
+}
 }  // namespace gprx
 
 extern "C" int64_t gprx_dev_panel_trace(int64_t* times, int64_t max_blocks) {

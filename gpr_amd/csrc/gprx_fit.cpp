@@ -1,5 +1,5 @@
 // gprx_fit.cpp — what produces a model's factor: the dense fit, the sharded fit, the LU fallback,
-// the fp64 refinement of fp32 fits, the explicit inverse and the append.
+// the fp64 refinement of fp32 fits, the explicit inverse, the append and the remove.
 #include "gprx_model.h"
 
 namespace gprx {
@@ -740,8 +740,118 @@ gprx_status model_append(gprx_model* M, const void* Xnew, const void* Ynew, int6
     return GPRX_OK;
 }
 
+// ---------------------------------------------------------------------------------------
+// gprx_model_remove: the samples [first, first + count) taken out of a fitted model by UPDATING
+// the Cholesky factor instead of refitting.  With the old factor partitioned at f = first and
+// f + r, [L11 0 0; L21 L22 0; L31 L32 L33], the reduced matrix has the factor [L11 0; L31 L33']
+// with L33' L33'^T = L33 L33^T + L32 L32^T: rows above f are kept, columns left of f only move
+// up by r, and the trailing block takes a rank-r update by Givens rotations (k_remove.hip, one
+// chained launch per 16 vectors), which also writes the identity padding and the new diagonal
+// blocks' inverses.  Column blocks before b0 = f / 128 are plain copies.  The labels are redone
+// exactly as the append does (label rows, chained forward panel solve over all rows, the fit's
+// reductions, chained back substitution into a second alpha).
+// Everything is built in second buffers (factor, Linv, X, Y, alpha: the update costs a second
+// factor's memory) and swapped in once the status words are known, so a refused update leaves
+// the fitted model as it was.  An LU-factored model, or more than GPRX_REMOVE_CUTOVER samples,
+// reduces the data and refits in full.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+gprx_status model_remove(gprx_model* M, int64_t first, int64_t count, uint32_t flags, gprx_fit_info* out) {
+    gprx_ctx* ctx = M->ctx;
+    GPRX_HIP(hipSetDevice(ctx->device));
+    hipStream_t s = ctx->stream;
+    const int d = M->d, m = M->m;
+    const int64_t n = M->n, f = first, r = count, n1 = n - r;
+    const uint32_t fit_flags = flags & (GPRX_FIT_NO_LU_FALLBACK | GPRX_FIT_F32_NO_REFINE);
+    M->trim_posterior_workspace();
+    // X and Y without rows [f, f + r) (row-major: the rows before and the rows after)
+    auto compact = [&](const DevBuf& from, DevBuf& to, int w) {
+        to.ensure(std::max(from.bytes, sizeof(T) * (size_t)n1 * w));
+        if (f > 0) GPRX_HIP(hipMemcpyAsync(to.p, from.p, sizeof(T) * f * w, hipMemcpyDeviceToDevice, s));
+        if (n1 > f)
+            GPRX_HIP(hipMemcpyAsync(to.as<T>() + f * w, from.as<T>() + (f + r) * w, sizeof(T) * (n1 - f) * w,
+                                    hipMemcpyDeviceToDevice, s));
+    };
+    compact(M->X, M->rmX, d);
+    compact(M->Y, M->rmY, m);
+    auto refit = [&](uint32_t fl) {  // full refit of the reduced data
+        GPRX_HIP(hipStreamSynchronize(s));
+        swap_buf(M->X, M->rmX);
+        swap_buf(M->Y, M->rmY);
+        M->n = n1;
+        M->drop_fit();
+        return model_fit<T>(M, fl, out);
+    };
+    if (M->method == 1 || r > GPRX_REMOVE_CUTOVER)
+        return refit(fit_flags | (M->method == 1 && M->lu_forced ? GPRX_FIT_FORCE_LU : 0u));
+
+    const int64_t mp = M->mp, np1 = round_up(n1, (int64_t)DB), ld0 = M->ld, ld1 = np1 + mp;
+    const int b0 = (int)(f / DB), nb1 = (int)(np1 / DB);
+    const int64_t c0 = (int64_t)b0 * DB;
+    M->rmA.ensure(sizeof(T) * ld1 * np1);
+    M->rmLinv.ensure(sizeof(T) * np1 * DB);
+    M->info.ensure(sizeof(int));
+    M->flag.ensure(sizeof(int));
+    M->red.ensure(sizeof(double) * (2 + 2 * (np1 / GT + 1)));
+    M->apAlpha.ensure(sizeof(T) * np1 * m);
+    const T* A0 = M->A.as<T>();
+    T* A1 = M->rmA.as<T>();
+    T* Li1 = M->rmLinv.as<T>();
+    launch_fit_status_init(M->info.as<int>(), M->flag.as<int>(), s);
+    GPRX_HIP(hipEventRecord(ctx->ev[0], s));
+    if (c0 > 0) {  // column blocks before b0: copied, the rows below f moved up by r, zero padding rows
+        GPRX_HIP(hipMemcpy2DAsync(A1, sizeof(T) * ld1, A0, sizeof(T) * ld0, sizeof(T) * f, c0, hipMemcpyDeviceToDevice, s));
+        if (n1 > f)
+            GPRX_HIP(hipMemcpy2DAsync(A1 + f, sizeof(T) * ld1, A0 + f + r, sizeof(T) * ld0, sizeof(T) * (n1 - f), c0,
+                                      hipMemcpyDeviceToDevice, s));
+        if (np1 > n1) GPRX_HIP(hipMemset2DAsync(A1 + n1, sizeof(T) * ld1, 0, sizeof(T) * (np1 - n1), c0, s));
+        GPRX_HIP(hipMemcpyAsync(Li1, M->Linv.p, sizeof(T) * c0 * DB, hipMemcpyDeviceToDevice, s));
+    }
+    GPRX_HIP(hipEventRecord(ctx->ev[1], s));
+    if (b0 < nb1) {  // (a tail removal that ends on a block boundary leaves nothing to update)
+        M->rmPairs.ensure(sizeof(T) * factor_update_ws_elems(nb1 - b0, (int)r));
+        launch_factor_update<T>(A0, ld0, A1, ld1, Li1, A0 + r + f * ld0, ld0, (int)r, f, r, n1, b0, nb1,
+                                M->rmPairs.as<T>(), M->info.as<int>(), ctx->ex, s);
+    }
+    GPRX_HIP(hipEventRecord(ctx->ev[2], s));
+    launch_label_rows<T>(M->rmY.as<T>(), n1, m, A1, ld1, np1, np1, mp, s);
+    for (int r0 = 0; r0 < m; r0 += DB)  // slabs of 128 label rows
+        launch_forward_panel_chain<T>(A1, ld1, np1, Li1, A1 + np1 + r0, ld1, std::min(DB, m - r0), M->info.as<int>(),
+                                      ctx->ex, s);
+    launch_fit_reductions<T>(A1, ld1, n1, np1, m, M->red.as<double>(), s);
+    launch_backsolve_chain<T>(A1, ld1, np1, m, Li1, M->apAlpha.as<T>(), M->info.as<int>(), ctx->ex, s);
+    GPRX_HIP(hipEventRecord(ctx->ev[3], s));
+    const FitStatus st = read_fit_status(M, s);
+    check_finite(st.flag);
+    check_sched(st.info);
+    if (st.info != INT_MAX) return refit(fit_flags);  // (no step above reports a pivot)
+    // publish
+    swap_buf(M->A, M->rmA);
+    swap_buf(M->Linv, M->rmLinv);
+    swap_buf(M->X, M->rmX);
+    swap_buf(M->Y, M->rmY);
+    swap_buf(M->alpha, M->apAlpha);
+    M->n = n1;
+    M->np = np1;
+    M->ld = ld1;
+    M->fit_done(0, false);
+    ensure_train_tables<T>(M);
+    if (out) {
+        std::memset(out, 0, sizeof(*out));
+        add_phase_times(ctx, out);
+        out->logdet = st.logdet;
+        out->datafit = st.datafit;
+        out->appended = -(int32_t)r;
+    }
+    if constexpr (std::is_same<T, float>::value) {
+        if (!(flags & GPRX_FIT_F32_NO_REFINE)) refine_f32(M, out);
+    }
+    return GPRX_OK;
+}
+
 #define GPRX_INST(T)                                                                                      \
     template gprx_status model_fit<T>(gprx_model*, uint32_t, gprx_fit_info*);                              \
+    template gprx_status model_remove<T>(gprx_model*, int64_t, int64_t, uint32_t, gprx_fit_info*);         \
     template gprx_status model_append<T>(gprx_model*, const void*, const void*, int64_t, uint32_t,         \
                                          gprx_fit_info*);                                                  \
     template void model_inverse<T>(gprx_model*);                                                           \

@@ -695,6 +695,20 @@ void launch_panel_rows(const T* P, int64_t ldp, int64_t rows, int64_t ncols, T* 
                        hipStream_t s);
 int64_t ap_trace_copy(long long* out, int64_t max_blocks);
 
+// Rank-r update L' L'^T = L L^T + X X^T of a lower factor by Givens rotations, one chained launch
+// per factor_update_width() vectors (k_remove.hip).  The new factor's blocks b0 .. nb - 1 (lower
+// tiles, whole, identity beyond row nlive) are written to dst (ldd) and, when Linv is not null,
+// their diagonal blocks' inverses to Linv + 128 * 128 * block; new row / column g >= f is read
+// from src (lds) at g + shift, x_iv from X[i + v ldx] for f <= i < nlive (zero above f), with
+// f inside block b0.  ws: factor_update_ws_elems(nb - b0, r) elements.  A timed-out wait sets
+// *info = -1.
+int factor_update_width();
+int64_t factor_update_ws_elems(int nblocks, int r);
+template <typename T>
+void launch_factor_update(const T* src, int64_t lds, T* dst, int64_t ldd, T* Linv, const T* X, int64_t ldx, int r,
+                          int64_t f, int64_t shift, int64_t nlive, int b0, int nb, T* ws, int* info, Exec& ex,
+                          hipStream_t s);
+
 // logdet partial = 2 sum log L_ii over i < n, datafit = sum of squares of the augmented
 // rows; results accumulated in double on the device (out[0], out[1]).
 template <typename T>

@@ -201,6 +201,10 @@ struct gprx_model {
     // gprx_model_append workspace: the new rows' panel, the sin/cos tables of the sample ranges it
     // builds from, the old partial block (restored when the update is refused) and the new alpha
     gprx::DevBuf apPanel, apTab, apStash, apAlpha, apPart;  // (+ the Schur update's split-K partials)
+    // gprx_model_remove workspace: the second factor, Linv, X and Y the reduced model is built in
+    // (swapped with A, Linv, X, Y when the status words are back, so a sliding window alternates
+    // between the two sets) and the rotations' (c, s) pairs (k_remove.hip)
+    gprx::DevBuf rmA, rmLinv, rmX, rmY, rmPairs;
     // a fit (a refit, an append, or the fit inside an LML call) and new data free the posterior
     // workspace when it is large (one big variance call must not leave too little HBM
     // for the next fit on the device); the LML's own gradient pass does not
@@ -264,7 +268,10 @@ struct gprx_model {
     //   append             in place: nothing until the status     fit_done(0, no); a refused update
     //                      words are back; full refit: fit,         restores A, Linv and drops nothing
     //                      then as fit
-    //   lml                as its fit                             as its fit, + inverse_done() on a
+    //   remove             update: nothing until the status       fit_done(0, no); a refused update
+    //                      words are back (built in second          leaves every buffer as it was
+    //                      buffers); full refit: fit, then as fit
+    //   lml               as its fit                             as its fit, + inverse_done() on a
     //                                                             sharded fit
     //   (first dense use of a sharded fit: dense_gathered())
     //
@@ -487,6 +494,8 @@ template <typename T>
 gprx_status model_append(gprx_model* M, const void* Xnew, const void* Ynew, int64_t k, uint32_t flags,
                          gprx_fit_info* out);
 template <typename T>
+gprx_status model_remove(gprx_model* M, int64_t first, int64_t count, uint32_t flags, gprx_fit_info* out);
+template <typename T>
 void model_inverse(gprx_model* M);
 template <typename T>
 void ensure_dense_factor(gprx_model* M);
@@ -540,4 +549,6 @@ gprx_status gprx_dev_bench_impl(gprx_dtype dtype, int32_t what, int64_t M, int64
                                 double* ms, Exec* ex);
 gprx_status gprx_dev_forward_panel_impl(gprx_dtype dtype, const void* L, int64_t n, void* R, int32_t rows,
                                         int32_t use_gemm, Exec* ex, hipStream_t s);
+gprx_status gprx_dev_factor_update_impl(gprx_dtype dtype, const void* L, int64_t n, const void* X, int32_t r,
+                                        void* Lout, void* LinvOut, Exec* ex, hipStream_t s);
 }  // namespace gprx

@@ -26,6 +26,7 @@ FIT_DISTRIBUTED = 2
 FIT_FORCE_LU = 8
 FIT_F32_NO_REFINE = 4
 APPEND_SOLVE_GEMM = 16  # Model.append: panel solves through trsm_rows, not the chained panel kernel
+REMOVE_CUTOVER = 128  # Model.remove: more samples than this in one call refit in full (GPRX_REMOVE_CUTOVER)
 LML_GRAD = 1
 LML_COMPAT = 2
 LML_DISTRIBUTED = 4
@@ -47,7 +48,7 @@ EXPORTED = [
     "gprx_model_set_kernel_matrix", "gprx_model_predict_kx", "gprx_model_posterior_cov_kx", "gprx_model_lml_dk",
     "gprx_model_set_sparse_cov", "gprx_sparse_lml",
     "gprx_device_alloc", "gprx_device_free", "gprx_device_upload", "gprx_device_download",
-    "gprx_model_append",
+    "gprx_model_append", "gprx_model_remove",
 ]
 
 
@@ -135,6 +136,8 @@ def lib():
         L.gprx_model_fit.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(FitInfo)]
         L.gprx_model_append.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_uint32, ctypes.POINTER(FitInfo)]
+        L.gprx_model_remove.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_uint32,
+                                        ctypes.POINTER(FitInfo)]
         L.gprx_model_get_alpha.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_set_alpha.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_predict.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -186,6 +189,10 @@ def lib():
                                           ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
         L.gprx_dev_forward_panel.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
                                              ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32]
+        L.gprx_dev_factor_update.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int64,
+                                             ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]
+        L.gprx_dev_factor_update_width.restype = ctypes.c_int32
+        L.gprx_dev_factor_update_width.argtypes = []
         L.gprx_dev_panel_trace.restype = ctypes.c_int64
         L.gprx_dev_panel_trace.argtypes = [ctypes.c_void_p, ctypes.c_int64]
         _lib = L
@@ -486,6 +493,26 @@ class Context:
                                              1 if use_gemm else 0))
         return V
 
+    def factor_update(self, L, X):
+        """(L', Linv) with L' L'^T = L L^T + X X^T for a lower factor L (n x n, n a multiple of
+        128) and X (n x r): the rotation kernel of Model.remove alone (gprx_dev_factor_update).
+        Linv is n x 128: the inverse of each 128 x 128 diagonal block of L'."""
+        L = np.ascontiguousarray(L)
+        X = np.ascontiguousarray(X, L.dtype)
+        if X.ndim == 1:
+            X = X[:, None]
+        if L.ndim != 2 or L.shape[0] != L.shape[1] or X.ndim != 2 or X.shape[0] != L.shape[0]:
+            raise ValueError("factor_update: L is n x n, X is n x r")
+        Lo, Li = np.empty_like(L), np.empty((L.shape[0], 128), L.dtype)
+        self._c(lib().gprx_dev_factor_update(self.h, _dt(L.dtype), _ptr(L), L.shape[0], _ptr(X), X.shape[1],
+                                             _ptr(Lo), _ptr(Li)))
+        return Lo, Li
+
+    @staticmethod
+    def factor_update_width():
+        """Vectors one launch of the rotation kernel carries (gprx_dev_factor_update_width)."""
+        return int(lib().gprx_dev_factor_update_width())
+
     def panel_trace(self, max_blocks=4096):
         """GPRX_BS_TRACE=1: per 128-column block of the last chained panel launch {start, streamed
         tiles done, the same, published} in 100 MHz ticks (gprx_dev_panel_trace)."""
@@ -671,6 +698,27 @@ class Model:
             raise
         self.n += k
         self._Xh = None if (dev or self._Xh is None) else np.concatenate([self._Xh, Xnew])
+        return info
+
+    def remove(self, first, count=1, flags=0):
+        """Take the samples [first, first + count) out of a fitted model by updating its Cholesky
+        factor with Givens rotations (gprx_model_remove): O((N - first)^2 count) instead of the
+        refit's O(N^3).  flags: FIT_NO_LU_FALLBACK, FIT_F32_NO_REFINE.  info.appended = -count, or
+        0 when the call had to refit in full (an LU factor, or count > REMOVE_CUTOVER)."""
+        first, count = int(first), int(count)
+        info = FitInfo()
+
+        def reduced():
+            self.n -= count
+            if self._Xh is not None:
+                self._Xh = np.concatenate([self._Xh[:first], self._Xh[first + count:]])
+        try:
+            self._c(lib().gprx_model_remove(self.h, first, count, flags, ctypes.byref(info)))
+        except GprxError as e:
+            if e.status in (2, 3):  # the full refit of the reduced data failed: the model holds them, unfitted
+                reduced()
+            raise
+        reduced()
         return info
 
     def dist_info(self):

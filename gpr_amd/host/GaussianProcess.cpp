@@ -93,10 +93,24 @@ void GaussianProcess<T>::AddSample(const VectorType& x, const VectorType& y) {
 }
 
 template <class T>
+void GaussianProcess<T>::RemoveSample(std::size_t index) {
+    if (index >= m_SampleVectors.size() || index >= m_LabelVectors.size())
+        throw std::string("GaussianProcess::RemoveSample: no sample with this index");
+    m_SampleVectors.erase(m_SampleVectors.begin() + index);
+    m_LabelVectors.erase(m_LabelVectors.begin() + index);
+    // the samples in front of the ones added since are the device's, less the queued removals
+    if (m_DataUploaded && m_DeviceSamples >= m_PendingRemovals.size() &&
+        index < m_DeviceSamples - m_PendingRemovals.size())
+        m_PendingRemovals.push_back(index);
+    m_Initialized = false;
+}
+
+template <class T>
 void GaussianProcess<T>::UploadState() {
     gprx_ctx* ctx = DefaultContext();
     const std::size_t n = m_SampleVectors.size();
-    if (!m_DataUploaded || !m_Model || m_DeviceSamples != n) {
+    if (!m_DataUploaded || !m_Model || m_DeviceSamples != n || !m_PendingRemovals.empty()) {
+        m_PendingRemovals.clear();
         const std::size_t d = m_InputDimension, m = m_OutputDimension;
         std::vector<T> X(n * d), Y(n * m);
         for (std::size_t i = 0; i < n; i++) {
@@ -225,30 +239,50 @@ void GaussianProcess<T>::Update() {
     if (!m_Initialized && n > 0 && m_LabelVectors.size() == n) {
         std::lock_guard<std::mutex> lk(m_DevMu);
         const bool svd = m_InvMethod == JacobiSVD || m_InvMethod == BDCSVD;
-        if (m_Model && m_DeviceFactor && m_FitCholesky && !svd && m_DataUploaded && m_DeviceSamples > 0 &&
-            m_DeviceSamples < n && m_FitSigma == m_Sigma && m_FitKernel == m_Kernel->ToString()) {
-            const std::size_t d = m_InputDimension, m = m_OutputDimension, n0 = m_DeviceSamples, c = n - n0;
-            std::vector<T> X(c * d), Y(c * m);
-            for (std::size_t i = 0; i < c; i++) {
-                for (std::size_t k = 0; k < d; k++) X[i * d + k] = m_SampleVectors[n0 + i][k];
-                for (std::size_t q = 0; q < m; q++) Y[i * m + q] = m_LabelVectors[n0 + i][q];
-            }
+        const std::size_t nrem = m_PendingRemovals.size();
+        // (the device's samples after the queued removals: at least one, all still in the lists)
+        if (m_Model && m_DeviceFactor && m_FitCholesky && !svd && m_DataUploaded && m_DeviceSamples > nrem &&
+            m_DeviceSamples - nrem <= n && (nrem > 0 || m_DeviceSamples < n) && m_FitSigma == m_Sigma &&
+            m_FitKernel == m_Kernel->ToString()) {
             gprx_fit_info fi;
-            const gprx_status st = gprx_model_append(m_Model, X.data(), Y.data(), (int64_t)c, GPRX_FIT_DEFAULT, &fi);
-            if (st != GPRX_OK) {  // whatever the device holds now, the next fit re-sends everything
-                m_DataUploaded = false;
+            auto check = [&](gprx_status st) {
+                if (st == GPRX_OK) return;
+                m_DataUploaded = false;  // whatever the device holds now, the next fit re-sends everything
                 m_DeviceFactor = false;
+                m_PendingRemovals.clear();
                 ThrowIfFailed(st, DefaultContext());
+            };
+            // (a removal or an append that had to refit in full leaves an LU factor behind: the
+            // device is then no longer updated, and what is still owed goes through Initialize())
+            std::size_t applied = 0;
+            for (; applied < nrem && m_FitCholesky; applied++) {
+                check(gprx_model_remove(m_Model, (int64_t)m_PendingRemovals[applied], 1, GPRX_FIT_DEFAULT, &fi));
+                m_DeviceSamples--;
+                m_FitCholesky = fi.method == 0;
             }
-            m_DeviceSamples = n;
-            m_FitCholesky = fi.method == 0;
-            m_RegressionVectors.resize(n, m_OutputDimension);
-            ThrowIfFailed(gprx_model_get_alpha(m_Model, m_RegressionVectors.data()), DefaultContext());
-            m_CoreValid = false;
-            m_CoreMatrix.resize(0, 0);
-            m_CoreSize = m_EfficientStorage ? 0 : n;
-            m_Initialized = true;
-            extended = true;
+            m_PendingRemovals.clear();
+            if (applied == nrem && m_FitCholesky && m_DeviceSamples < n) {
+                const std::size_t d = m_InputDimension, m = m_OutputDimension, n0 = m_DeviceSamples, c = n - n0;
+                std::vector<T> X(c * d), Y(c * m);
+                for (std::size_t i = 0; i < c; i++) {
+                    for (std::size_t k = 0; k < d; k++) X[i * d + k] = m_SampleVectors[n0 + i][k];
+                    for (std::size_t q = 0; q < m; q++) Y[i * m + q] = m_LabelVectors[n0 + i][q];
+                }
+                check(gprx_model_append(m_Model, X.data(), Y.data(), (int64_t)c, GPRX_FIT_DEFAULT, &fi));
+                m_DeviceSamples = n;
+                m_FitCholesky = fi.method == 0;
+            }
+            if (applied == nrem && m_DeviceSamples == n) {
+                m_RegressionVectors.resize(n, m_OutputDimension);
+                ThrowIfFailed(gprx_model_get_alpha(m_Model, m_RegressionVectors.data()), DefaultContext());
+                m_CoreValid = false;
+                m_CoreMatrix.resize(0, 0);
+                m_CoreSize = m_EfficientStorage ? 0 : n;
+                m_Initialized = true;
+                extended = true;
+            } else {
+                m_DataUploaded = false;
+            }
         }
     }
     if (!extended) Initialize();

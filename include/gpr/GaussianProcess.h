@@ -72,16 +72,21 @@ public:
     void operator=(const Self&) = delete;
 
     void AddSample(const VectorType& x, const VectorType& y);
+    // Erases sample `index` and its label (throws when there is none).  A sample that is resident
+    // on the device is queued for Update(), which takes it out of the device factor
+    // (gprx_model_remove) instead of refitting; Initialize() refits as always.  Not in the reference.
+    void RemoveSample(std::size_t index);
     virtual VectorType Predict(const VectorType& x);
     virtual VectorType PredictDerivative(const VectorType& x, MatrixType& D);
     virtual TScalarType operator()(const VectorType& x, const VectorType& y);
     TScalarType GetCredibleInterval(const VectorType& x);
     virtual void Initialize();
-    // Initialize() for a GP that only GREW since its last device fit: when the device holds a
-    // Cholesky factor made with the current kernel and sigma and the only change since is c >= 1
-    // AddSample calls, the c new samples extend that factor (gprx_model_append, O(N^2 c)) instead
-    // of the O(N^3) refit; in every other state this is Initialize().  Opt-in: Initialize() and
-    // the calls that imply it always refit.  Not in the reference.
+    // Initialize() for a GP that only GREW or SHRANK since its last device fit: when the device
+    // holds a Cholesky factor made with the current kernel and sigma and the only changes since are
+    // RemoveSample and AddSample calls, the queued removals are applied to that factor in order
+    // (gprx_model_remove), then the samples added since extend it (gprx_model_append, O(N^2 c)),
+    // instead of the O(N^3) refit; in every other state this is Initialize().  Opt-in:
+    // Initialize() and the calls that imply it always refit.  Not in the reference.
     virtual void Update();
 
     // Batched, device-native forms (one launch for all rows; not in the reference).
@@ -148,6 +153,10 @@ protected:
                                   // Update() only the samples added since
     std::size_t m_DeviceSamples = 0;  // samples resident on the device (UploadState re-sends all
                                       // of them when it differs from the sample count)
+    // RemoveSample calls on device-resident samples since the device data was last in step: the
+    // index each had on the device once the earlier ones are applied (Update applies them in order;
+    // UploadState re-sends everything instead)
+    std::vector<std::size_t> m_PendingRemovals;
     // the device factor's provenance (FitDevice, Update): a Cholesky factor, and the kernel and
     // sigma it was made with -- Update() extends it only while these still hold
     bool m_FitCholesky = false;

@@ -117,7 +117,8 @@ typedef struct gprx_fit_info {
     double ms_refine;    /* fp32 models: device time of the fp64 iterative refinement */
     double refine_delta; /* fp32 models: |last correction|_inf / |alpha|_inf (0 if not refined) */
     int32_t refine_steps;/* fp32 models: refinement steps taken */
-    int32_t appended;    /* gprx_model_append: rows added by extending the factor (0: a full refit) */
+    int32_t appended;    /* gprx_model_append: rows added by extending the factor (0: a full refit);
+                            gprx_model_remove: -count when the factor was updated (0: a full refit) */
 } gprx_fit_info;
 
 /* ---- library / context ---------------------------------------------------------- */
@@ -253,6 +254,24 @@ gprx_status gprx_model_fit(gprx_model* model, uint32_t flags, gprx_fit_info* inf
                                       instead of the chained panel kernel (k_append.hip) */
 gprx_status gprx_model_append(gprx_model* model, const void* Xnew, const void* Ynew, int64_t k, uint32_t flags,
                               gprx_fit_info* info);
+/* The counterpart of gprx_model_append: the samples [first, first + count) leave a FITTED model
+ * without the O(N^3) refit.  Rows of the factor above `first` are kept, the columns left of it
+ * only move up, and the trailing block takes a rank-count UPDATE (an addition, never a downdate)
+ * by Givens rotations, O((N - first)^2 count) (k_remove.hip); the labels' forward solve and alpha
+ * are then redone against the whole factor as in an append.  The reduced model is built in second
+ * buffers (the call needs a second factor's memory) and replaces the fitted one only when it is
+ * complete.  predict, posterior_cov, core_matrix and lml then see the n - count samples left.
+ * flags: GPRX_FIT_NO_LU_FALLBACK, GPRX_FIT_F32_NO_REFINE as for a fit.
+ * info->appended = -count when the factor was updated.  A model whose factor is the LU, or
+ * count > GPRX_REMOVE_CUTOVER, reduces the data and refits in full (info->appended = 0).  The
+ * update's time grows with count (one pass over the trailing block per 16 samples): measured on
+ * an MI355X it beats the refit for single samples at N = 16384 only, so a caller
+ * that drops many samples at once should set the reduced data and fit.  GPRX_ERR_STATE, model untouched: not fitted, a
+ * caller-evaluated kernel, a sparse-covariance model, a sharded fit or context.  GPRX_ERR_DIM,
+ * model untouched: first < 0, count < 1, first + count > n, or count == n (nothing would be
+ * left). */
+#define GPRX_REMOVE_CUTOVER 128
+gprx_status gprx_model_remove(gprx_model* model, int64_t first, int64_t count, uint32_t flags, gprx_fit_info* info);
 /* m_RegressionVectors (lib/GaussianProcess.cpp:661) -> host, N x m. */
 gprx_status gprx_model_get_alpha(gprx_model* model, void* alpha);
 /* Install regression vectors (n x m, row-major) read back by GaussianProcess::Load

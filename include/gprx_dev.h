@@ -120,6 +120,16 @@ gprx_status gprx_dev_fexp(gprx_ctx* ctx, const double* x, int64_t n, double* y);
 gprx_status gprx_dev_forward_panel(gprx_ctx* ctx, gprx_dtype dtype, const void* L, int64_t n, void* R, int32_t rows,
                                    int32_t use_gemm);
 int64_t gprx_dev_panel_trace(int64_t* times, int64_t max_blocks);
+/* Parity hook for the rotation kernel of gprx_model_remove (k_remove.hip) alone: the factor of
+ * L L^T + X X^T for the host row-major lower factor L (n x n, n a multiple of 128) and the host
+ * row-major X (n x r), by Givens rotations in the kernel's order (column block, column, vector).
+ * Lout: the new factor, n x n row-major (zeros above the diagonal); LinvOut: the inverse of each
+ * 128 x 128 diagonal block of it, n x 128 row-major (block b in rows [128 b, 128 b + 128)).
+ * gprx_dev_factor_update_width() is the number of vectors one launch carries: a wider X runs
+ * further passes in place on the new factor. */
+gprx_status gprx_dev_factor_update(gprx_ctx* ctx, gprx_dtype dtype, const void* L, int64_t n, const void* X, int32_t r,
+                                   void* Lout, void* LinvOut);
+int32_t gprx_dev_factor_update_width(void);
 #ifdef __cplusplus
 }
 #endif
