@@ -25,7 +25,8 @@ all: $(LIBDIR)/libgprx.so $(LIBDIR)/libgpr_amd.so cpptests oracle
 # 4 x 4 store / reduce loops around the inlined kernel-tree evaluation; its size exceeds LLVM's
 # default pragma budget (the request was silently dropped: -Wpass-failed), so it is raised for
 # these two files (fewer VGPRs, no scratch: the loop indices stay compile-time register indices).
-$(BUILD)/k_build.o $(BUILD)/k_lml.o: HIPFLAGS += -mllvm -pragma-unroll-threshold=200000
+$(BUILD)/k_build.o $(BUILD)/k_lml.o $(BUILD)/codeobj/k_build.elf $(BUILD)/codeobj/k_lml.elf: \
+	HIPFLAGS += -mllvm -pragma-unroll-threshold=200000
 
 $(BUILD)/%.o: gpr_amd/csrc/%.hip $(HDRS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -60,14 +61,41 @@ pt_sched_asan: $(PT_SCHED_SRCS) $(PT_SCHED_HDRS) | $(BUILD)
 		-o $(BUILD)/pt_sched_test_asan $(PT_SCHED_SRCS)
 	$(BUILD)/pt_sched_test_asan
 
+# `make codeobj`: the device side of every source alone, with the file's own flags and a fixed
+# compilation-unit id (without one the ELF carries a symbol hashed from the file's path and text),
+# then one line per file of sha256 hashes: the whole ELF, .text, .rodata (the kernel descriptors)
+# and the notes (the amdhsa metadata: VGPR / SGPR / spill counts, LDS sizes).  A pure refactor of
+# a kernel file leaves the listing as its parent's: run it in both checkouts and diff.  It only
+# hashes; it needs no GPU and is not part of `all`.
+LLVMBIN  ?= $(dir $(HIPCC))../llvm/bin
+CODEOBJ  := $(BUILD)/codeobj
+CO_FLAGS := --offload-device-only --no-gpu-bundle-output -cuid=gprx
+CO_ELFS  := $(sort $(patsubst gpr_amd/csrc/%.hip,$(CODEOBJ)/%.elf,$(HIP_SRCS)) \
+                   $(patsubst gpr_amd/csrc/%.cpp,$(CODEOBJ)/%.elf,$(CPP_SRCS)))
+
+$(CODEOBJ)/%.elf: gpr_amd/csrc/%.hip $(HDRS) | $(CODEOBJ)
+	$(HIPCC) $(HIPFLAGS) $(CO_FLAGS) -c $< -o $@
+
+$(CODEOBJ)/%.elf: gpr_amd/csrc/%.cpp $(HDRS) | $(CODEOBJ)
+	$(HIPCC) $(HIPFLAGS) $(CO_FLAGS) -x hip -c $< -o $@
+
+codeobj: $(CO_ELFS)
+	@printf '%-18s %-16s %-16s %-16s %-16s\n' file elf .text .rodata notes; \
+	h() { sha256sum | cut -c1-16; }; \
+	for f in $(CO_ELFS); do \
+	  for s in text rodata; do $(LLVMBIN)/llvm-objcopy -O binary --only-section=.$$s $$f $$f.$$s; done; \
+	  printf '%-18s %s %s %s %s\n' $$(basename $$f .elf) $$(h < $$f) $$(h < $$f.text) $$(h < $$f.rodata) \
+	    $$($(LLVMBIN)/llvm-readelf --notes $$f | h); \
+	done
+
 oracle:
 	$(MAKE) -s -C oracle
 
-$(BUILD) $(LIBDIR):
+$(BUILD) $(LIBDIR) $(CODEOBJ):
 	mkdir -p $@
 
 clean:
 	rm -rf $(BUILD) $(LIBDIR)/*.so $(CPPTESTS)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean cpptests pt_sched_asan
+.PHONY: all oracle clean cpptests pt_sched_asan codeobj

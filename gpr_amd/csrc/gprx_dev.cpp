@@ -11,20 +11,6 @@
 #include "gprx_model.h"
 #include "pt_sched.h"
 
-namespace gprx {
-template <typename T>
-void launch_gemm_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t M, int64_t N,
-                    int64_t K, T alpha, T beta, bool lower, hipStream_t s);
-template <typename T>
-void launch_diag_public(T* Akk, int64_t ld, T* Lk, int* info, int64_t col0, hipStream_t s, int ph = 3);
-template <typename T>
-void launch_diag_prof(T* Akk, int64_t ld, T* Lk, int* info, long long* prof, hipStream_t s);
-namespace pt {
-template <typename T>
-void launch_diag_bench(int variant, T* A, int64_t ld, T* Linv, int* info, long long* prof, int reps, hipStream_t s);
-}
-}  // namespace gprx
-
 using namespace gprx;
 
 template <typename T>

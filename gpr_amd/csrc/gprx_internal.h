@@ -473,10 +473,11 @@ struct TileBuild {
     int* flag;
     int mode;
 };
-// Per diagonal block k, TP_STRIDE state words of the split diagonal step (k_ptiles.hip): [0..7]
-// TPART(k, p)'s phase, [TP_DPAN] DIAGX(k)'s published panels (the progressive TPART(k + 1, .)
-// follow it)
-constexpr int TP_STRIDE = 16, TP_DPAN = 8;  // (up to eight parts: pt_sched.h tp_parts)
+// Per diagonal block k, TP_STRIDE state words of the split diagonal step (k_pt_split.h): [0..7]
+// TPART(k, p)'s phase; [8..15] unused.  (Word 8 was the panel counter of the progressive parts,
+// removed; commit 15ef139 still has them.  The stride stays 16: it is a run-time stride of the
+// kernel's address arithmetic.)
+constexpr int TP_STRIDE = 16;  // (up to eight parts: pt_sched.h tp_parts)
 
 // Distributed tile factorisation (k_ptiles.hip, potrf_tiles_kernel<T, true>; gprx_dist.cpp):
 // this rank's view of a factorisation whose row blocks are dealt over g ranks in groups of gb
@@ -626,6 +627,19 @@ void launch_gemm_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int6
 template <typename T>
 void launch_gemm_nt_splitk(T* C, int64_t ldc, int64_t cstride, const T* A, int64_t lda, const T* B, int64_t ldb,
                            int64_t M, int64_t N, int64_t K, int P, T alpha, bool lower, hipStream_t s);
+
+// Developer timing hooks (gprx_dev.cpp): one stand-alone 128 x 128 diagonal factor of the stream
+// formulation (k_potrf.hip; ph: the phases to run, prof: its phase ticks), and the tile
+// factorisation's diagonal factors back to back in one workgroup (k_ptiles.hip diag_bench_kernel;
+// variant 0 rank-8, 1 blocked, 2 look-ahead).
+template <typename T>
+void launch_diag_public(T* Akk, int64_t ld, T* Lk, int* info, int64_t col0, hipStream_t s, int ph = 3);
+template <typename T>
+void launch_diag_prof(T* Akk, int64_t ld, T* Lk, int* info, long long* prof, hipStream_t s);
+namespace pt {
+template <typename T>
+void launch_diag_bench(int variant, T* A, int64_t ld, T* Linv, int* info, long long* prof, int reps, hipStream_t s);
+}  // namespace pt
 
 // Split-K rank-k accumulation on the tile mainloop (k_syrk.hip): partial p (of P) +=
 // alpha A[:, pK:(p+1)K] A[:, pK:(p+1)K]^T into C + p*cstride, lower triangle of the leading

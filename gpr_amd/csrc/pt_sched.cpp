@@ -281,7 +281,7 @@ Schedule make_schedule(int nc, int nr, int W, int near, int P, const Cost& cm0, 
         if (split && k >= 1) {  // TPART(k, np-1..0), then DIAGX(k) on their products
             int tp[8];
             for (int c = cm.np - 1; c >= 0; c--) {
-                tp[c] = D.add(T_TPART, k, c, 0, 0, cm.prog ? cm.tpart_prog : cm.tpart + cm.tpart_c * (c + 1));
+                tp[c] = D.add(T_TPART, k, c, 0, 0, cm.tpart + cm.tpart_c * (c + 1));
                 D.dep(tp[c], diagx[k - 1]);
                 D.dep(tp[c], last_upd[(size_t)k * nc + (k - 1)]);
                 D.dep(tp[c], last_upd[(size_t)k * nc + k]);  // phase 2 starts from A_kk
@@ -445,8 +445,7 @@ DistSched make_schedule_dist(int nc, bool inv, int W, int near, int P, int g, in
         int tp[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
         if (split && k >= 1)  // TPART(k, np-1..0) on the owner of row block k
             for (int c = cm.np - 1; c >= 0; c--) {
-                tp[c] = D.add(T_TPART, k, c, 0, 0,
-                              (cm.prog && own(k - 1) == own(k)) ? cm.tpart_prog : cm.tpart + cm.tpart_c * (c + 1), own(k));
+                tp[c] = D.add(T_TPART, k, c, 0, 0, cm.tpart + cm.tpart_c * (c + 1), own(k));
                 D.dep(tp[c], linv(k - 1, own(k)));
                 D.dep(tp[c], last_upd[(size_t)k * nci + (k - 1)]);
                 D.dep(tp[c], last_upd[(size_t)k * nci + k]);  // phase 2 starts from A_kk
@@ -568,7 +567,6 @@ Params::Params() {
     pair_tail_set = geti("GPRX_PT_PAIR_TAIL", cm.pair_tail, 0);
     getd("GPRX_PT_TPART_US", cm.tpart);
     getd("GPRX_PT_DIAGXS_US", cm.diagx_s);
-    getd("GPRX_PT_TPARTP_US", cm.tpart_prog);
     getd("GPRX_PT_KLAB_US", cm.klab);
     geti("GPRX_PT_LABEL", label, any);
     int idp = 1, idt = 1;  // (0 turns them off)
@@ -621,7 +619,7 @@ Schedule best_schedule(int nc, int nr, const Params& pr, int P, bool build, int 
 // the split diagonal step runs for both precisions (f64: S through the look-ahead factor's LDS
 // image; f32: S in place for the rank-8 factor), unless GPRX_PT_SPLIT=0
 // (the parts of a step wait for each other: at least tp_parts workgroups)
-bool split_for(bool f64, int P) { return P >= tp_parts(f64 && DIAG_LA) && SPLIT_CODE && params().split != 0; }
+bool split_for(bool f64, int P) { return P >= tp_parts(f64) && params().split != 0; }
 
 }  // namespace pt
 

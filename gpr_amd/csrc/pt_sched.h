@@ -10,6 +10,7 @@
 #include <hip/hip_vector_types.h>
 
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "gprx_error.h"
@@ -24,35 +25,16 @@ enum { T_DIAGX = 0, T_TRSM = 1, T_UPD = 2, T_BUILD = 3, T_TPART = 4, T_UPD2 = 5 
 
 namespace pt {
 
-// GPRX_TP_PROG (A/B builds): the progressive parts (tpart_prog) and DIAGX's panel counter.  Off
-// by default: same-box A/Bs (profiles/r04c_*, r04d_*) measured the chain step unchanged (C2
-// 1829 us against 1815 for the Linv form without the panel counter; the counter's stores and
-// drains cost DIAGX ~1.3 us per step, the early X_3 saves ~2 us of the parts' T phase, and the
-// parts' S phase, not T, dominates after DIAGX(k-1) ends) and C3 0.1-0.4% slower.
-#ifdef GPRX_TP_PROG
-constexpr bool tp_linv_form() { return false; }
-#else
-constexpr bool tp_linv_form() { return true; }
-#endif
-// TPART workgroups per split diagonal step: f64 (the Linv form) eight -- part p = C + 4 h takes
-// the column groups C, 7 - C of T's rows 64 h .. 64 h + 63 and the S quarter of tile-rows C, 7 - C
-// over T's columns 64 h .. 64 h + 63 (tpart_run8) -- f32 and the progressive form four
-// (GPRX_TP_PARTS4: four for f64 too)
-#ifdef GPRX_TP_PARTS4
-constexpr int tp_parts(bool f64) { return (void)f64, 4; }
-#else
-constexpr int tp_parts(bool f64) { return f64 && tp_linv_form() ? 8 : 4; }
-#endif
-#ifdef GPRX_NO_SPLIT  // (A/B builds: the split diagonal step compiled out)
-constexpr bool SPLIT_CODE = false;
-#else
-constexpr bool SPLIT_CODE = true;
-#endif
-#ifndef GPRX_DIAG_RANK8
-constexpr bool DIAG_LA = true;
-#else
-constexpr bool DIAG_LA = false;
-#endif
+// TPART workgroups per split diagonal step: f64 eight -- part p = C + 4 h takes the column
+// groups C, 7 - C of T's rows 64 h .. 64 h + 63 and the S quarter of tile-rows C, 7 - C over T's
+// columns 64 h .. 64 h + 63 (tpart_run8: half the four-part form's MFMAs per wave in both phases,
+// DESIGN 4.1.1a "Eight parts") -- f32 four (tpart_run).
+constexpr int tp_parts(bool f64) { return f64 ? 8 : 4; }
+// The diagonal factor by precision: f64 the blocked factor with look-ahead on an LDS image
+// (diag_factor_la), which the split step's parts feed through the S buffer; f32 the rank-8
+// register image, its block read from memory.
+template <typename T>
+constexpr bool diag_la = std::is_same<T, double>::value;
 
 struct Cost {  // per-task durations (us, one CU), calibrated from GPRX_PT_TRACE timelines
     double k128 = 17.1;  // per 128-deep slice of a full tile update
@@ -69,11 +51,6 @@ struct Cost {  // per-task durations (us, one CU), calibrated from GPRX_PT_TRACE
     // 2 us and factors; step 54.4 us)
     double tpart = 11.5, tpart_c = 0.0;
     double diagx_s = 44.0, early_s = 2.0;
-    // the progressive parts (f64, tpart_prog; DIAGX(k-1) on the same rank): they follow DIAGX(k-1)'s
-    // panels and publish S this long after its end (X_3, T and S remain after its last fact32,
-    // ~8 us before its end)
-    double tpart_prog = 2.5;
-    bool prog = false;  // this schedule is for the progressive form (set by the callers)
     int np = 4;         // TPART tasks per split step (tp_parts; set by the callers)
     // a paired update (T_UPD2) per panel, relative to two single-tile panels (the 256 x 128
     // mainloop's probe rate against the 128 x 128 tile's: 0.877 / 0.901)
@@ -123,11 +100,10 @@ struct Params {
     double push_us = 4.0, rel_us = 2.0;
     int near_for(int nc) const { return near >= 0 ? near : (nc <= 64 ? 1 : 0); }
     Params();
-    // the cost model for a precision: the progressive parts are the f64 look-ahead factor's
+    // the cost model for a precision
     Cost cost(bool f64) const {
         Cost c = cm;
-        c.prog = f64 && DIAG_LA && !tp_linv_form();
-        c.np = tp_parts(f64 && DIAG_LA);
+        c.np = tp_parts(f64);
         return c;
     }
 };

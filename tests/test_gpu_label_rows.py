@@ -1,4 +1,4 @@
-"""The narrow label row of the single-GPU tile factorisation (k_mma.h tile_mma_rows16, k_ptiles.hip
+"""The narrow label row of the single-GPU tile factorisation (k_mma.h tile_mma_rows16, k_pt_ops.h
 tile_gemm_rows16): with at most 16 labels the label row block's updates multiply its first 16
 rows only, and the row leaves the paired updates.  Per element the narrow product runs the MFMA
 steps of the full tile in the same k order before the same subtraction, so against the full-tile
