@@ -88,6 +88,33 @@ codeobj: $(CO_ELFS)
 	    $$($(LLVMBIN)/llvm-readelf --notes $$f | h); \
 	done
 
+# `make codeobj-kernels`: the same ELFs, one line per kernel instead of per file, so that a
+# kernel that changes files (or loses a neighbour) can still be compared with its parent: the
+# mangled name, the file, a sha256 hash of the kernel's instruction text (its disassembly without
+# the `// address: encoding` comments, the symbol's address line and the `...` that stands for
+# the zero padding after a file's last kernel, which is layout and not code) and its amdhsa
+# metadata entry: VGPRs, AGPRs, SGPRs, LDS bytes, scratch bytes, SGPR and VGPR spills.  Sorted by name:
+# two checkouts diff cleanly when the file column is ignored.  It only hashes and prints.
+codeobj-kernels: $(CO_ELFS)
+	@printf '%s %s %s %s\n' kernel file text 'vgpr agpr sgpr lds scratch sgpr_spill vgpr_spill'; \
+	for f in $(CO_ELFS); do \
+	  $(LLVMBIN)/llvm-readelf --notes $$f | awk ' \
+	    /^  - \.agpr_count:/ { ag = $$3 } \
+	    /^    \.group_segment_fixed_size:/ { lds = $$2 } \
+	    /^    \.private_segment_fixed_size:/ { scr = $$2 } \
+	    /^    \.sgpr_count:/ { sg = $$2 } \
+	    /^    \.sgpr_spill_count:/ { ss = $$2 } \
+	    /^    \.symbol:/ { sym = $$2; sub(/\.kd$$/, "", sym) } \
+	    /^    \.vgpr_count:/ { vg = $$2 } \
+	    /^    \.vgpr_spill_count:/ { vs = $$2 } \
+	    /^    \.wavefront_size:/ { print sym, vg, ag, sg, lds, scr, ss, vs }' | \
+	  while read -r sym meta; do \
+	    printf '%s %s %s %s\n' $$sym $$(basename $$f .elf) \
+	      $$($(LLVMBIN)/llvm-objdump -d --disassemble-symbols=$$sym $$f | grep '^[[:space:]]' | \
+	         sed -e 's|[[:space:]]*//.*$$||' -e '/^[[:space:]]*\.\.\.$$/d' | sha256sum | cut -c1-16) "$$meta"; \
+	  done; \
+	done | sort
+
 oracle:
 	$(MAKE) -s -C oracle
 
@@ -98,4 +125,4 @@ clean:
 	rm -rf $(BUILD) $(LIBDIR)/*.so $(CPPTESTS)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all oracle clean cpptests pt_sched_asan codeobj
+.PHONY: all oracle clean cpptests pt_sched_asan codeobj codeobj-kernels

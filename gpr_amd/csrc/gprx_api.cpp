@@ -13,6 +13,23 @@ gprx_status fail(gprx_ctx* ctx, gprx_status st, const std::string& msg) {
     return st;
 }
 
+// Exec is host-only state of the context that owns it: the tile factorisation's cached
+// schedules and the device ints the chained launches use as counters and flags.
+Exec::~Exec() {
+    pt_state_free(pt);
+    if (scratch) (void)hipFree(scratch);
+}
+
+int* Exec::scratch_ints(size_t n) {
+    if (n > scratch_n) {
+        if (scratch) GPRX_HIP(hipFree(scratch));
+        scratch = nullptr;
+        GPRX_HIP(hipMalloc(&scratch, sizeof(int) * n));
+        scratch_n = n;
+    }
+    return scratch;
+}
+
 }  // namespace gprx
 
 using namespace gprx;
@@ -20,7 +37,7 @@ using namespace gprx;
 // The prologue of a model entry point, in the order every one of them keeps: the NULL check
 // (`args_ok` with the function's own message), `pre` (checks that run before the lock; true = there
 // is nothing to do), the context's and the model's locks, the profiler binding (CALL_PROF; after
-// the lock: resolved, streams drained, before it is released), hipSetDevice (CALL_DEVICE), `body`.
+// the lock: resolved, the stream drained, before it is released), hipSetDevice (CALL_DEVICE), `body`.
 // An entry point whose state checks come between the lock and the device selection selects the
 // device in its body; fit and append select it in model_fit / model_append.
 enum : unsigned { CALL_PROF = 1, CALL_DEVICE = 2 };
@@ -69,37 +86,13 @@ static gprx_ctx* ctx_new(int device) {
     GPRX_HIP(hipSetDevice(device));
     gprx_ctx* ctx = new gprx_ctx();
     ctx->device = device;
-    // The main stream carries the factorisation's critical path (panel chain): give it the
-    // highest priority so its small kernels are dispatched ahead of the bulk trailing update
-    // running on the aux stream.
+    // The context's one stream carries every launch of a call in order: the persistent tile
+    // factorisation, the chained solves, the GEMMs and the reductions.  It has the highest
+    // priority, so its kernels are dispatched ahead of other work on the device.
     int prio_lo = 0, prio_hi = 0;
     GPRX_HIP(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
     GPRX_HIP(hipStreamCreateWithPriority(&ctx->stream, hipStreamNonBlocking, prio_hi));
-    // The aux stream (bulk trailing updates) is kept off a few CUs so the panel chain's
-    // one-workgroup diagonal kernels never queue behind a full-chip GEMM: GPRX_RESERVE_CU
-    // CUs (default 0 = off: measured no gain; 8 = one per XCD when CUs are numbered XCD-major) are excluded from its mask.
-    int reserve = 0;
-    if (const char* e = std::getenv("GPRX_RESERVE_CU")) reserve = std::atoi(e);
-    hipDeviceProp_t prop;
-    GPRX_HIP(hipGetDeviceProperties(&prop, device));
-    const int ncu = prop.multiProcessorCount;
-    if (reserve > 0 && reserve < ncu) {
-        std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-        const int per = std::max(1, reserve / 8), stride = std::max(1, ncu / 8);
-        int excluded = 0;
-        for (int i = 0; i < ncu; i++) {
-            const bool res = (i % stride) < per && excluded < reserve;
-            if (res) excluded++;
-            else mask[i / 32] |= 1u << (i % 32);
-        }
-        GPRX_HIP(hipExtStreamCreateWithCUMask(&ctx->aux, (uint32_t)mask.size(), mask.data()));
-    } else {
-        GPRX_HIP(hipStreamCreateWithPriority(&ctx->aux, hipStreamNonBlocking, prio_lo));
-    }
-    GPRX_HIP(hipStreamCreateWithPriority(&ctx->aux2, hipStreamNonBlocking, prio_hi));
     ctx->ex.s0 = ctx->stream;
-    ctx->ex.s1 = ctx->aux;
-    ctx->ex.s2 = ctx->aux2;
     for (auto& e : ctx->ev) GPRX_HIP(hipEventCreate(&e));
     return ctx;
 }
@@ -118,8 +111,6 @@ void gprx_ctx_destroy(gprx_ctx* ctx) {
     for (auto& e : ctx->ev)
         if (e) (void)hipEventDestroy(e);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
-    if (ctx->aux2) (void)hipStreamDestroy(ctx->aux2);
     delete ctx->hc;
     // abort, not destroy: local, never waits on the peers (a communicator whose collective
     // timed out, or whose peers already left, would block ncclCommDestroy); every stream of

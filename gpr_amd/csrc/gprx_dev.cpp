@@ -72,33 +72,6 @@ static gprx_status bench_impl(int what, int64_t M, int64_t N, int64_t K, int ite
             (void)hipMemcpy(h, pr, sizeof(h), hipMemcpyDeviceToHost);
             ms[0] = 1e3 * tms / reps;
             for (int i = 0; i < 8; i++) ms[1 + i] = (double)h[i] / reps;
-        } else if (what == 6) {  // in-kernel phase ticks of the diagonal kernel: ms[0..4] per launch
-            T* A = (T*)alloc(sizeof(T) * DB * DB * (size_t)iters);
-            T* L = (T*)alloc(sizeof(T) * DB * DB);
-            long long* pr = (long long*)alloc(sizeof(long long) * 8);
-            (void)hipMemset(pr, 0, sizeof(long long) * 8);
-            for (int it = 0; it < iters; it++)
-                hipLaunchKernelGGL(dev_fill_spd<T>, dim3((DB * DB + 255) / 256), dim3(256), 0, s, A + (size_t)it * DB * DB,
-                                   (int64_t)DB, (int64_t)DB, (uint64_t)it);
-            for (int it = 0; it < iters; it++) launch_diag_prof<T>(A + (size_t)it * DB * DB, DB, L, info, pr, s);
-            long long h[8];
-            (void)hipStreamSynchronize(s);
-            (void)hipMemcpy(h, pr, sizeof(h), hipMemcpyDeviceToHost);
-            for (int i = 0; i < 5; i++) ms[i] = (double)h[i] / iters;
-        } else if (what == 0) {
-            const int ph = 3;
-            T* A = (T*)alloc(sizeof(T) * DB * DB * (size_t)iters);
-            T* L = (T*)alloc(sizeof(T) * DB * DB);
-            for (int it = 0; it < iters; it++)
-                hipLaunchKernelGGL(dev_fill_spd<T>, dim3((DB * DB + 255) / 256), dim3(256), 0, s, A + (size_t)it * DB * DB,
-                                   (int64_t)DB, (int64_t)DB, (uint64_t)it);
-            launch_diag_public<T>(A, DB, L, info, 0, s, ph);  // warm
-            (void)hipEventRecord(e0, s);
-            for (int it = 1; it < iters; it++) launch_diag_public<T>(A + (size_t)it * DB * DB, DB, L, info, 0, s, ph);
-            (void)hipEventRecord(e1, s);
-            (void)hipEventSynchronize(e1);
-            (void)hipEventElapsedTime(&tms, e0, e1);
-            *ms = tms / std::max(1, iters - 1);
         } else if (what == 1 || what == 2) {
             const int64_t ld = M;
             T* C = (T*)alloc(sizeof(T) * ld * N);
@@ -118,67 +91,30 @@ static gprx_status bench_impl(int what, int64_t M, int64_t N, int64_t K, int ite
             (void)hipEventSynchronize(e1);
             (void)hipEventElapsedTime(&tms, e0, e1);
             *ms = tms / iters;
-        } else if (what == 3 || what == 4 || what == 5 || what == 9 || what == 10) {
+        } else if (what == 5 || what == 9 || what == 10) {
+            // 9: the tile factorisation; 5 / 10: the per-block / chained back substitution of its
+            // factor (the factorisation outside the timed region)
             const int64_t n = M;
             T* A = (T*)alloc(sizeof(T) * n * n);
             T* Li = (T*)alloc(sizeof(T) * n * DB);
             T* z = (T*)alloc(sizeof(T) * n);
             T* al = (T*)alloc(sizeof(T) * n);
-            Exec single;
-            single.s0 = s;
-            single.s1 = nullptr;
-            Exec& use = (what == 4) ? ex : single;
             double total = 0;
             for (int it = 0; it < iters + 1; it++) {
                 hipLaunchKernelGGL(dev_fill_spd<T>, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, s, A, n, n,
                                    (uint64_t)it);
                 (void)hipMemsetD32Async((hipDeviceptr_t)info, INT_MAX, 1, s);
-                if (what == 5 || what == 10) potrf_blocked<T>(A, n, n, n, Li, info, use);
+                if (what == 5 || what == 10) potrf_tiles<T>(A, n, n, n, Li, info, ex);
                 (void)hipEventRecord(e0, s);
                 if (what == 5) launch_backsolve<T>(A, n, n - DB, 1, Li, z, al, s);
                 else if (what == 10) launch_backsolve_chain<T>(A, n, n - DB, 1, Li, al, info, ex, s);
-                else if (what == 9) potrf_tiles<T>(A, n, n, n, Li, info, ex);
-                else potrf_blocked<T>(A, n, n, n, Li, info, use);
+                else potrf_tiles<T>(A, n, n, n, Li, info, ex);
                 (void)hipEventRecord(e1, s);
                 (void)hipEventSynchronize(e1);
                 (void)hipEventElapsedTime(&tms, e0, e1);
                 if (it > 0) total += tms;
             }
             *ms = total / iters;
-        } else if (what == 7 || what == 8) {  // the same sequences replayed from a captured hipGraph
-            const int64_t n = M;
-            T* A = (T*)alloc(sizeof(T) * n * n);
-            T* Li = (T*)alloc(sizeof(T) * n * DB);
-            T* z = (T*)alloc(sizeof(T) * n);
-            T* al = (T*)alloc(sizeof(T) * n);
-            hipLaunchKernelGGL(dev_fill_spd<T>, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, s, A, n, n,
-                               (uint64_t)0);
-            if (what == 8) potrf_blocked<T>(A, n, n, n, Li, info, ex);
-            (void)hipStreamSynchronize(s);
-            hipGraph_t g = nullptr;
-            hipGraphExec_t ge = nullptr;
-            GPRX_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed));
-            if (what == 8) launch_backsolve<T>(A, n, n - DB, 1, Li, z, al, s);
-            else potrf_blocked<T>(A, n, n, n, Li, info, ex);
-            GPRX_HIP(hipStreamEndCapture(s, &g));
-            GPRX_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-            double total = 0;
-            for (int it = 0; it < iters + 1; it++) {
-                if (what == 7) {
-                    hipLaunchKernelGGL(dev_fill_spd<T>, dim3((unsigned)((n * n + 255) / 256)), dim3(256), 0, s, A, n, n,
-                                       (uint64_t)it);
-                    (void)hipMemsetD32Async((hipDeviceptr_t)info, INT_MAX, 1, s);
-                }
-                (void)hipEventRecord(e0, s);
-                GPRX_HIP(hipGraphLaunch(ge, s));
-                (void)hipEventRecord(e1, s);
-                (void)hipEventSynchronize(e1);
-                (void)hipEventElapsedTime(&tms, e0, e1);
-                if (it > 0) total += tms;
-            }
-            *ms = total / iters;
-            (void)hipGraphExecDestroy(ge);
-            (void)hipGraphDestroy(g);
         } else {
             throw Error{GPRX_ERR_ARG, "dev bench: unknown case"};
         }

@@ -440,7 +440,7 @@ gprx_status model_fit(gprx_model* M, uint32_t flags, gprx_fit_info* out) {
     M->start_dense_fit();
     const int64_t n = M->n, np = round_up(n, (int64_t)DB), mp = round_up(M->m, GT);
     // the explicit inverse rides along in the tile factorisation as np identity rows
-    const bool want_inv = M->want_inv && potrf_uses_tiles();
+    const bool want_inv = M->want_inv;
     const int64_t ld = np + mp + (want_inv ? np : 0);
     M->np = np;
     M->mp = mp;
@@ -470,7 +470,7 @@ gprx_status model_fit(gprx_model* M, uint32_t flags, gprx_fit_info* out) {
                                 M->flag.as<int>());
         train_features<T>(M, true, np);
         const KCanon<T>* kdev = M->kfit.put(K, s);
-        if (env_kbuild() != KBUILD_SEPARATE && potrf_uses_tiles())
+        if (env_kbuild() != KBUILD_SEPARATE)
             tb = pairs_tile_build<T>(K, kdev, M->featU.as<T>(), M->featV.as<T>(), np, M->d, n, sigma2,
                                      M->flag.as<int>());
         if (!tb.mode)
@@ -487,7 +487,7 @@ gprx_status model_fit(gprx_model* M, uint32_t flags, gprx_fit_info* out) {
         potrf_tiles<T>(M->A.as<T>(), ld, np, ld, M->Linv.as<T>(), M->info.as<int>(), ctx->ex, tb.mode ? &tb : nullptr,
                        want_inv ? (int)(np / GT) : 0, false, mp == GT ? M->m : GT);
     } else {
-        potrf_auto<T>(M->A.as<T>(), ld, np, ld, M->Linv.as<T>(), M->info.as<int>(), ctx->ex);
+        potrf_tiles<T>(M->A.as<T>(), ld, np, ld, M->Linv.as<T>(), M->info.as<int>(), ctx->ex);
     }
     GPRX_HIP(hipEventRecord(ctx->ev[2], s));
     launch_fit_reductions<T>(M->A.as<T>(), ld, n, np, M->m, M->red.as<double>(), s);
@@ -695,7 +695,7 @@ gprx_status model_append(gprx_model* M, const void* Xnew, const void* Ynew, int6
             launch_gemm_nt<T>(S, ld1, A1 + n0, ld1, A1 + n0, ld1, nap, nap, n0, T(-1), T(1), true, s);
         }
     }
-    potrf_auto<T>(S, ld1, nap, nap, Li1 + n0 * DB, M->info.as<int>(), ctx->ex);
+    potrf_tiles<T>(S, ld1, nap, nap, Li1 + n0 * DB, M->info.as<int>(), ctx->ex);
     GPRX_HIP(hipEventRecord(ctx->ev[2], s));
     launch_label_rows<T>(M->Y.as<T>(), n1, m, A1, ld1, np1, np1, mp, s);
     if (gemm) {

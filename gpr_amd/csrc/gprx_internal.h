@@ -285,7 +285,8 @@ __device__ inline void gsincos(float x, float* s, float* c) { sincosf(x, s, c); 
 
 // ---------------------------------------------------------------------------------
 // Opt-in per-kernel device timing (gprx_ctx_set_stats): HIP events around every launch
-// of the classes below, on the stream the kernel is launched on.
+// of the classes below, on the stream the kernel is launched on.  The values index the profile
+// slots, so they stay; KC_DIAG has no producer left (its kernel went with the stream Cholesky).
 // ---------------------------------------------------------------------------------
 enum KClass { KC_BUILD = 0, KC_DIAG, KC_TRSM, KC_UPDATE, KC_BACKSOLVE, KC_PREDICT, KC_LML_GRAD, KC_INVERSE, KC_OTHER,
               KC_TILES, KC_POSTERIOR, KC_COUNT };
@@ -435,27 +436,18 @@ template <typename T>
 void launch_label_rows(const T* Y, int64_t n, int m, T* A, int64_t ld, int64_t row0, int64_t ncols, int64_t mp,
                        hipStream_t s);
 
-// Blocked right-looking Cholesky of the leading np x np block of A (ld rows; rows np..ld
-// are extra rows solved along: they end up holding (L^{-1} B)^T).  Linv receives the
-// inverses of the np/DB diagonal blocks (DB x DB each, column-major).  info: device int,
-// first failing column (1-based) via atomicMin semantics (initialised to INT_MAX).
+// A context's execution state for the persistent and chained launches (host-only; members in
+// gprx_api.cpp, next to the context that owns it).
 struct PtState;             // tile-dataflow potrf: cached schedules + counters (k_ptiles.hip)
 void pt_state_free(PtState* p);
 struct Exec {
-    hipStream_t s0 = nullptr;  // main stream (panel chain)
-    hipStream_t s1 = nullptr;  // look-ahead stream (bulk trailing updates); may be null
-    hipStream_t s2 = nullptr;  // second look-ahead stream (next panel's later columns); may be null
-    std::vector<hipEvent_t> ev;
+    hipStream_t s0 = nullptr;  // the context's stream
     PtState* pt = nullptr;
     int* scratch = nullptr;  // device ints for in-launch counters/flags (grown on demand)
     size_t scratch_n = 0;
     int* scratch_ints(size_t n);
-    hipEvent_t event(size_t i);
     ~Exec();
 };
-int outer_block();
-template <typename T>
-void potrf_blocked(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info, Exec& ex);
 // The covariance build fused into the tile factorisation: each lower tile of the leading
 // np x np block is built from the pair-statistics features (k_pairs.h) by a BUILD task of
 // the same persistent launch, ahead of its first consumer, instead of by a separate kernel.
@@ -598,8 +590,12 @@ void launch_sub(const T* X, const T* Y, T* Z, int64_t e, hipStream_t s);
 template <typename T>
 TileBuild<T> pairs_tile_build(const KCanon<T>& K, const KCanon<T>* Kd, const T* FU, const T* FV, int64_t nf, int d,
                               int64_t n, T sigma2, int* flag);
-// Same contract, one persistent launch: 128x128 tile tasks scheduled on the device by
-// dependency counters (k_ptiles.hip).  A timed-out dependency wait sets *info = -1.
+// Cholesky of the leading np x np block of A (ld rows; rows np..nrows are extra rows solved
+// along: they end up holding (L^{-1} B)^T).  Linv receives the inverses of the np/DB diagonal
+// blocks (DB x DB each, column-major).  info: device int, first failing column (1-based) via
+// atomicMin semantics (initialised to INT_MAX).  One persistent launch: 128x128 tile tasks
+// scheduled on the device by dependency counters (k_ptiles.hip).  A timed-out dependency
+// wait sets *info = -1.
 // ni > 0: the last ni row blocks of the nrows are the identity, set up here, and leave as
 // L^{-T} (upper triangular, ni = np / 128): the inverse factor riding along as extra rows,
 // each identity block updated only from its own column block on.
@@ -609,15 +605,11 @@ TileBuild<T> pairs_tile_build(const KCanon<T>& K, const KCanon<T>* Kd, const T* 
 template <typename T>
 void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info, Exec& ex,
                  const TileBuild<T>* build = nullptr, int ni = 0, bool build_only = false, int lab_live = GT);
-// C (lower) = A B^T where both operands vanish left of their row (LAUUM shape), k_potrf.hip
+// C (lower) = A B^T where both operands vanish left of their row (LAUUM shape), k_gemm.hip
 template <typename T>
 void launch_gemm_nt_kskip(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t M, int64_t N,
                           int64_t K, hipStream_t s);
-// Factorisation used by the fit paths: potrf_tiles unless GPRX_POTRF=streams.
-template <typename T>
-void potrf_auto(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info, Exec& ex);
-bool potrf_uses_tiles();
-// Generic C = beta C + alpha A B^T on GT-multiples (column-major).  lower: only tiles
+// Generic C = beta C + alpha A B^T on GT-multiples (column-major), k_gemm.hip.  lower: only tiles
 // with col-tile <= row-tile are computed, and inside diagonal tiles only row >= col.
 template <typename T>
 void launch_gemm_nt(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, int64_t ldb, int64_t M, int64_t N,
@@ -628,14 +620,8 @@ template <typename T>
 void launch_gemm_nt_splitk(T* C, int64_t ldc, int64_t cstride, const T* A, int64_t lda, const T* B, int64_t ldb,
                            int64_t M, int64_t N, int64_t K, int P, T alpha, bool lower, hipStream_t s);
 
-// Developer timing hooks (gprx_dev.cpp): one stand-alone 128 x 128 diagonal factor of the stream
-// formulation (k_potrf.hip; ph: the phases to run, prof: its phase ticks), and the tile
-// factorisation's diagonal factors back to back in one workgroup (k_ptiles.hip diag_bench_kernel;
-// variant 0 rank-8, 1 blocked, 2 look-ahead).
-template <typename T>
-void launch_diag_public(T* Akk, int64_t ld, T* Lk, int* info, int64_t col0, hipStream_t s, int ph = 3);
-template <typename T>
-void launch_diag_prof(T* Akk, int64_t ld, T* Lk, int* info, long long* prof, hipStream_t s);
+// Developer timing hook (gprx_dev.cpp): the tile factorisation's diagonal factors back to back in
+// one workgroup (k_ptiles.hip diag_bench_kernel; variant 0 rank-8, 1 blocked, 2 look-ahead).
 namespace pt {
 template <typename T>
 void launch_diag_bench(int variant, T* A, int64_t ld, T* Linv, int* info, long long* prof, int reps, hipStream_t s);
@@ -654,7 +640,8 @@ bool launch_gemm_tall(T* C, int64_t ldc, const T* A, int64_t lda, const T* B, in
                       int64_t K, T alpha, T beta, hipStream_t s);
 
 // Back substitution L^T alpha = z with z given as the m augmented rows (row-major output
-// alpha: np x m, ld m).  Uses the diagonal-block inverses.
+// alpha: np x m, ld m).  Uses the diagonal-block inverses.  Per-block launches (k_bsolve.hip):
+// the sparse GP's form; the fits use launch_backsolve_chain below.
 template <typename T>
 void launch_backsolve(const T* A, int64_t ld, int64_t np, int m, const T* Linv, T* z, T* alpha, hipStream_t s);
 
@@ -724,7 +711,7 @@ void launch_factor_update(const T* src, int64_t lds, T* dst, int64_t ldd, T* Lin
                           hipStream_t s);
 
 // logdet partial = 2 sum log L_ii over i < n, datafit = sum of squares of the augmented
-// rows; results accumulated in double on the device (out[0], out[1]).
+// rows; results accumulated in double on the device (out[0], out[1]).  k_bsolve.hip.
 template <typename T>
 void launch_fit_reductions(const T* A, int64_t ld, int64_t n, int64_t np, int m, double* out,
                            hipStream_t s);  // out: 2 + 2 * (np / 128) doubles

@@ -168,9 +168,7 @@ struct gprx_ctx {
     gprx::HostColl* hc = nullptr;  // host collectives of a multi-process context (RCCL or the caller's)
     bool peer = false;          // gprx_ctx_create_peer: the caller's collective, no RCCL
     int cu_slot = 0, cu_slots = 1;  // GPRX_DIST_SHARED_GPU: ranks of one GPU split its CUs
-    hipStream_t stream = nullptr;
-    hipStream_t aux = nullptr;  // look-ahead stream of the factorisation
-    hipStream_t aux2 = nullptr;  // second look-ahead stream (next panel's later columns)
+    hipStream_t stream = nullptr;  // the context's one stream (highest priority)
     gprx::Exec ex;
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     gprx::Prof prof;
@@ -305,7 +303,7 @@ struct gprx_model {
 namespace gprx {
 
 // Per-call profiler binding: sets the thread's current profiler and resolves the
-// recorded events (after draining both streams) when the call returns.
+// recorded events (after draining the stream) when the call returns.
 struct ProfBind {
     gprx_ctx* ctx;
     explicit ProfBind(gprx_ctx* c) : ctx(c) { g_prof = (c && c->prof.on) ? &c->prof : nullptr; }
@@ -313,8 +311,6 @@ struct ProfBind {
     ~ProfBind() {
         if (ctx && ctx->prof.on) {
             (void)hipStreamSynchronize(ctx->stream);
-            (void)hipStreamSynchronize(ctx->aux);
-            (void)hipStreamSynchronize(ctx->aux2);
             ctx->prof.resolve();
         }
         g_prof = nullptr;
@@ -322,7 +318,7 @@ struct ProfBind {
 };
 
 // Every model call holds its context's mutex, then the model's (always in that order): the
-// device work of a model runs on the context's streams and uses the context's scratch (the
+// device work of a model runs on the context's stream and uses the context's scratch (the
 // tile factorisation's ticket and counter words, its cached schedules, the timing events),
 // so two models of one context must not interleave their launches -- a second fit's memset
 // of the ticket counter landing between another fit's memset and launch leaves that launch

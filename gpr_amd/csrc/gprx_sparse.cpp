@@ -199,7 +199,7 @@ static void sparse_normal_eq(gprx_ctx* ctx, SparseNE<T>& st, const gprx_kernel_d
     // ---- S = L L^T with b in the extra rows -> RV; S^{-1} -> RM -----------------------------
     dLinv.ensure(sizeof(T) * Mp * DB);
     GPRX_HIP(hipMemsetD32Async((hipDeviceptr_t)dinfo.p, INT_MAX, 1, s));
-    potrf_auto<T>(dS.as<T>(), ld, Mp, ld, dLinv.as<T>(), dinfo.as<int>(), ctx->ex);
+    potrf_tiles<T>(dS.as<T>(), ld, Mp, ld, dLinv.as<T>(), dinfo.as<int>(), ctx->ex);
     int hinfo = 0;
     download(&hinfo, dinfo.p, sizeof(int), s);
     check_sched(hinfo);
@@ -216,7 +216,7 @@ static void sparse_factor_kmm(gprx_ctx* ctx, SparseNE<T>& st) {
     int hinfo = 0;
     st.dLinvK.ensure(sizeof(T) * Mp * DB);
     GPRX_HIP(hipMemsetD32Async((hipDeviceptr_t)st.dinfo.p, INT_MAX, 1, s));
-    potrf_auto<T>(st.dK.template as<T>(), Mp, Mp, Mp, st.dLinvK.template as<T>(), st.dinfo.template as<int>(), ctx->ex);
+    potrf_tiles<T>(st.dK.template as<T>(), Mp, Mp, Mp, st.dLinvK.template as<T>(), st.dinfo.template as<int>(), ctx->ex);
     download(&hinfo, st.dinfo.p, sizeof(int), s);
     check_sched(hinfo);
     if (hinfo != INT_MAX)

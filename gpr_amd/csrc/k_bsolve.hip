@@ -1,11 +1,15 @@
-// k_bsolve.hip — back substitution alpha = L^{-T} z in ONE launch (gfx950).
+// k_bsolve.hip — the fit's epilogue on gfx950: what runs after the factorisation.
+//   launch_fit_reductions    log det and data fit from the factor and its label rows
+//   launch_backsolve_chain   back substitution alpha = L^{-T} z in ONE launch (the fits)
+//   launch_forward_chain     forward substitution z = L^{-1} r in one launch (fp32 refinement)
+//   launch_backsolve         the per-block back substitution (the sparse GP)
 //
-// Replaces the second half of the regression-vector solve (alpha = C Y with C = (K+s^2 I)^{-1},
+// The chained back substitution replaces the second half of the regression-vector solve (alpha = C Y with C = (K+s^2 I)^{-1},
 // lib/GaussianProcess.cpp:642-672, ComputeRegressionVectors; the reference forms C explicitly
 // with lapack::lu_invert, include/LAPACKUtils.h:38-56).  Here z = L^{-1} Y is already in the
 // augmented rows of the factor (potrf), and
 //     alpha_k = Linv_k^T ( z_k - sum_{j > k} L_jk^T alpha_j )        (128-row blocks k)
-// is a chain over the blocks from the last to the first.  The stream version launched two
+// is a chain over the blocks from the last to the first.  The per-block form launches two
 // kernels per block (~18 us each, 2.2 ms at N = 16384); here one workgroup per block streams
 // its column panel L_{k+1..,k} (contiguous in the column-major factor) as the alpha_j it needs
 // are published, and publishes alpha_k when done: the critical path per block is one
@@ -433,5 +437,169 @@ template void launch_backsolve_chain<double>(const double*, int64_t, int64_t, in
                                              Exec&, hipStream_t, const uint64_t*, const int64_t*);
 template void launch_backsolve_chain<float>(const float*, int64_t, int64_t, int, const float*, float*, int*, Exec&,
                                             hipStream_t, const uint64_t*, const int64_t*);
+
+// ======================================================================================
+// Per-block back substitution  L^T alpha = z   (z: m rows of length np, alpha: np x m row-major)
+// The same solve as the chain above with two launches per 128-block.  Who uses which: the fit,
+// its fp32 refinement, append and remove (gprx_fit.cpp) use the chained form; the sparse GP
+// (gprx_sparse.cpp) uses this one.
+// ======================================================================================
+template <typename T>
+__global__ void copy_aug_kernel(const T* __restrict__ A, int64_t ld, int64_t np, int m, T* __restrict__ z) {
+    int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (int64_t)m * np) return;
+    int64_t r = e / np, c = e % np;
+    z[e] = A[np + r + c * ld];
+}
+
+// alpha_j = Linv_j^T z_j  (one workgroup): the 128x128 block is staged into LDS with
+// coalesced loads (row q of the image = column q of Linv), then thread q forms
+// sum_{p >= q} Linv[p][q] z[p] from LDS.
+template <typename T>
+__global__ __launch_bounds__(256) void backsolve_alpha_kernel(int64_t np, int m, const T* __restrict__ Linv,
+                                                              const T* __restrict__ z, T* __restrict__ alpha,
+                                                              int64_t j0) {
+    __shared__ T sLi[DB][DB + 1];
+    __shared__ T sz[DB];
+    const int t = threadIdx.x;
+#pragma unroll 8
+    for (int u = 0; u < DB * DB / 256; u++) {
+        const int e = t + 256 * u;
+        sLi[e / DB][e % DB] = Linv[e];
+    }
+    for (int r = 0; r < m; r++) {
+        if (t < DB) sz[t] = z[(int64_t)r * np + j0 + t];
+        __syncthreads();
+        if (t < DB) {
+            T acc = 0;
+            for (int p = t; p < DB; p++) acc = fma(sLi[t][p], sz[p], acc);
+            alpha[(j0 + t) * m + r] = acc;
+        }
+        __syncthreads();
+    }
+}
+
+// z[c] -= sum_p L[j0+p][c] alpha_j[p] for c < j0.  16 lanes per column (each lane 8
+// consecutive rows = 64 contiguous bytes), 4 columns per wave, 16 columns per workgroup.
+constexpr int BS_COLS_WG = 16;
+template <typename T>
+__global__ __launch_bounds__(256) void backsolve_update_kernel(const T* __restrict__ A, int64_t ld, int64_t np, int m,
+                                                               const T* __restrict__ alpha, T* __restrict__ z,
+                                                               int64_t j0) {
+    const int t = threadIdx.x;
+    const int lane = t & 63, w = t >> 6;
+    const int sub = lane >> 4, l16 = lane & 15;
+    const int64_t c = (int64_t)blockIdx.x * BS_COLS_WG + w * 4 + sub;
+    const bool ok = c < j0;
+    T Lv[8];
+    if (ok) {
+        const T* Lc = A + j0 + c * ld + l16 * 8;
+#pragma unroll
+        for (int e = 0; e < 8; e++) Lv[e] = Lc[e];
+    }
+    for (int r = 0; r < m; r++) {
+        T v = 0;
+        if (ok) {
+#pragma unroll
+            for (int e = 0; e < 8; e++) v = fma(Lv[e], alpha[(j0 + l16 * 8 + e) * m + r], v);
+        }
+        v += __shfl_xor(v, 8);
+        v += __shfl_xor(v, 4);
+        v += __shfl_xor(v, 2);
+        v += __shfl_xor(v, 1);
+        if (ok && l16 == 0) z[(int64_t)r * np + c] -= v;
+    }
+}
+
+template <typename T>
+void launch_backsolve(const T* A, int64_t ld, int64_t np, int m, const T* Linv, T* z, T* alpha, hipStream_t s) {
+    const int64_t e = (int64_t)m * np;
+    ProfScope ps(KC_BACKSOLVE, s, 2.0 * (double)np * np * m / 2.0, (double)sizeof(T) * np * (np + 1) / 2.0);
+    hipLaunchKernelGGL(copy_aug_kernel<T>, dim3((unsigned)((e + 255) / 256)), dim3(256), 0, s, A, ld, np, m, z);
+    for (int64_t j0 = np - DB; j0 >= 0; j0 -= DB) {
+        hipLaunchKernelGGL(backsolve_alpha_kernel<T>, dim3(1), dim3(256), 0, s, np, m,
+                           Linv + (j0 / DB) * (int64_t)DB * DB, (const T*)z, alpha, j0);
+        if (j0 > 0)
+            hipLaunchKernelGGL(backsolve_update_kernel<T>, dim3((unsigned)((j0 + BS_COLS_WG - 1) / BS_COLS_WG)),
+                               dim3(256), 0, s, A, ld, np, m, (const T*)alpha, z, j0);
+    }
+}
+
+// ======================================================================================
+// The fit's reductions, run between the factorisation and the back substitution of every fit:
+// logdet = 2 sum log L_ii, datafit = || z ||^2  (double accumulation)
+// ======================================================================================
+// log det = 2 sum log L_ii and the data fit z^T z (z = L^{-1} Y in the label rows), in two
+// steps with a fixed summation order: per 128-row block partials, then their sum.  (One
+// 1024-thread block striding over the strided diagonal took 61 us at N = 16384.)
+template <typename T>
+__global__ __launch_bounds__(256) void fit_reduce_part_kernel(const T* __restrict__ A, int64_t ld, int64_t n,
+                                                              int64_t np, int m, double* __restrict__ part) {
+    __shared__ double s0[256], s1[256];
+    const int t = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * 128;
+    double a = 0, b = 0;
+    if (t < 128 && r0 + t < n) a = log((double)A[r0 + t + (r0 + t) * ld]);
+    for (int e = t; e < 128 * m; e += 256) {
+        const int64_t c = r0 + e / m;
+        const int r = e % m;
+        if (c < np) {
+            const double v = (double)A[np + r + c * ld];
+            b += v * v;
+        }
+    }
+    s0[t] = a;
+    s1[t] = b;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) {
+            s0[t] += s0[t + off];
+            s1[t] += s1[t + off];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        part[2 * blockIdx.x] = s0[0];
+        part[2 * blockIdx.x + 1] = s1[0];
+    }
+}
+
+__global__ __launch_bounds__(256) void fit_reduce_sum_kernel(const double* __restrict__ part, int nb,
+                                                             double* __restrict__ out) {
+    __shared__ double s0[256], s1[256];
+    const int t = threadIdx.x;
+    double a = 0, b = 0;
+    for (int k = t; k < nb; k += 256) {
+        a += part[2 * k];
+        b += part[2 * k + 1];
+    }
+    s0[t] = a;
+    s1[t] = b;
+    __syncthreads();
+    for (int off = 128; off > 0; off >>= 1) {
+        if (t < off) {
+            s0[t] += s0[t + off];
+            s1[t] += s1[t + off];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        out[0] = 2.0 * s0[0];
+        out[1] = s1[0];
+    }
+}
+
+// out[0] = log det, out[1] = z^T z; out holds 2 + 2 * (np / 128) doubles (the partials after)
+template <typename T>
+void launch_fit_reductions(const T* A, int64_t ld, int64_t n, int64_t np, int m, double* out, hipStream_t s) {
+    const int nb = (int)((np + 127) / 128);
+    hipLaunchKernelGGL(fit_reduce_part_kernel<T>, dim3((unsigned)nb), dim3(256), 0, s, A, ld, n, np, m, out + 2);
+    hipLaunchKernelGGL(fit_reduce_sum_kernel, dim3(1), dim3(256), 0, s, (const double*)(out + 2), nb, out);
+}
+
+template void launch_backsolve<double>(const double*, int64_t, int64_t, int, const double*, double*, double*, hipStream_t);
+template void launch_backsolve<float>(const float*, int64_t, int64_t, int, const float*, float*, float*, hipStream_t);
+template void launch_fit_reductions<double>(const double*, int64_t, int64_t, int64_t, int, double*, hipStream_t);
+template void launch_fit_reductions<float>(const float*, int64_t, int64_t, int64_t, int, double*, hipStream_t);
 
 }  // namespace gprx

@@ -1,14 +1,14 @@
 // k_ptiles.hip — tile-dataflow Cholesky in ONE persistent launch (gfx950).
 //
-// Replaces the same reference step as potrf_blocked (lapack::lu_invert -> dgetrf_+dgetri_,
+// Replaces the reference's factorise/invert step (lapack::lu_invert -> dgetrf_+dgetri_,
 // include/LAPACKUtils.h:38-56, 85-97, called from GaussianProcess::InvertKernelMatrix,
 // lib/GaussianProcess.cpp:545-559) with K + sigma^2 I = L L^T, the forward solve z = L^{-1} Y
-// riding along as extra row blocks, exactly as k_potrf.hip does -- but scheduled on the device.
+// riding along as extra row blocks, scheduled on the device.
 //
-// Why: in the stream formulation every step of the panel chain (diagonal factor -> trsm ->
-// next-column update) is a kernel that must wait for CU slots held by the bulk trailing
-// GEMM, so at N = 16384 the chain (18 ms alone) stretches to most of the 37 ms
-// factorisation.  Here one workgroup per CU runs a loop over a ticket list of 128x128 TILE
+// Why: in a stream formulation (one kernel per step; removed) every step of the
+// panel chain (diagonal factor -> trsm -> next-column update) is a kernel that must wait for CU
+// slots held by the bulk trailing GEMM, so at N = 16384 the chain (18 ms alone) stretched to
+// most of the 37 ms factorisation.  Here one workgroup per CU runs a loop over a ticket list of 128x128 TILE
 // TASKS (pt_sched.h: T_DIAGX .. T_UPD2) with per-tile dependency counters in HBM:
 //
 //   BUILD(i,j)       the covariance tile A_ij from the pair statistics (k_pairs.h build_tile_sum)

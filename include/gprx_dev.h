@@ -9,18 +9,16 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
-/* what: 0 = diagonal 128-block factor+inverse, 1 = gemm_nt (C -= A B^T), 2 = lower gemm_nt,
- *       3 = full potrf of an n x n SPD matrix (single stream), 4 = potrf with look-ahead,
- *       5 = back substitution (m = 1) of an n x n factor,
- *       6 = diagonal kernel phase profile: ms must hold 5 doubles, receiving the mean
- *           s_memtime ticks per launch of (load, solve phases, update phases, store, total),
- *       7 = potrf with look-ahead replayed from a captured hipGraph, 8 = backsolve from a graph,
- *       9 = potrf as one persistent tile-dataflow launch (potrf_tiles),
+/* what: 1 = gemm_nt (C -= A B^T), 2 = lower gemm_nt,
+ *       5 = per-block back substitution (m = 1) of an n x n factor (launch_backsolve),
+ *       9 = potrf of an n x n SPD matrix as one persistent tile-dataflow launch (potrf_tiles),
  *      10 = back substitution as one flag-chained launch (launch_backsolve_chain),
  *      11 / 12 / 13 = the tile engine's diagonal-block factor, variant what - 11 (rank-8 /
  *           blocked / look-ahead): ms must hold 9 doubles: ms[0] = us per factor, ms[1..5] =
  *           phase ticks (100 MHz), ms[6..8] = fact32 core cycles (GPRX_FACT32_PROF builds).
- * For 1/2: (M, N, K) are the gemm sizes; for 3/4/5: M = n.  Returns the mean device time
+ *       0, 3, 4, 6, 7, 8 timed the stream-based Cholesky, which was removed: like any unknown
+ *           case they return GPRX_ERR_ARG (the other numbers keep their meaning).
+ * For 1/2: (M, N, K) are the gemm sizes; for 5/9/10: M = n.  Returns the mean device time
  * per call over `iters` calls (HIP events) in *ms. */
 gprx_status gprx_dev_bench(gprx_ctx* ctx, gprx_dtype dtype, int32_t what, int64_t M, int64_t N, int64_t K,
                            int32_t iters, double* ms);

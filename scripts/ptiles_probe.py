@@ -1,4 +1,4 @@
-"""GPU probe of the tile-dataflow potrf: correctness vs numpy and timing vs the stream path."""
+"""GPU probe of the tile-dataflow potrf: correctness vs numpy and timing."""
 import ctypes, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -31,8 +31,7 @@ def run(what, M, iters=3):
 
 
 for n in [int(x) for x in os.environ.get("PT_TN", "4096,16384").split(",")]:
-    for what, name in ((9, "tiles"), (4, "streams")):
-        ms = run(what, n)
-        res[f"potrf_{n}_{name}"] = {"ms": ms, "tflops": n ** 3 / 3 / ms / 1e9}
-        print(n, name, ms, flush=True)
+    ms = run(9, n)
+    res[f"potrf_{n}_tiles"] = {"ms": ms, "tflops": n ** 3 / 3 / ms / 1e9}
+    print(n, "tiles", ms, flush=True)
 print(json.dumps(res, indent=1))

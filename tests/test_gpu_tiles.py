@@ -190,7 +190,7 @@ def test_posterior_tall_gemms_match_128_tiles(tmp_path):
 @pytest.mark.gpu
 def test_posterior_repeatable_in_place_solves():
     """The row solves' diagonal-block products run in place (k_predict.hip trsm_rows: R_k =
-    R_k Linv_k^T); launch_gemm_nt keeps them on whole-row tiles (k_potrf.hip), since with 64 x 64
+    R_k Linv_k^T); launch_gemm_nt keeps them on whole-row tiles (k_gemm.hip), since with 64 x 64
     tiles the workgroup of columns 64..127 could read columns its neighbour had already
     overwritten -- an intermittent error in a 64-query block (seen once in ~150 processes at
     N = 8192, Q = 4096).  Repeated variances of one fit agree to the last bit."""
