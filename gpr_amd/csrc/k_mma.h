@@ -1,16 +1,30 @@
-// k_mma.h — the 128x128 f64/f32 MFMA tile machinery shared by the tile-dataflow
-// factorisation (k_ptiles.hip) and the pair-statistics kernels (k_pairs.hip).
+// k_mma.h — the f64/f32 MFMA tile products shared by the tile-dataflow factorisation
+// (k_pt_ops.h), the pair-statistics kernels (k_pairs.h, k_pairs.hip) and the stand-alone GEMMs
+// (k_syrk.hip, k_dsolve.hip).
 //
-// One 512-thread workgroup (8 waves of 64x32 outputs, v_mfma_f64_16x16x4f64 /
-// v_mfma_f32_16x16x4f32) computes acc = A B^T for a 128x128 tile, A and B being 128-row
-// column-major operand panels K deep.  Operands are staged by LDS-DMA (global_load_lds_dwordx4,
-// no VGPRs) into a ring of NBUF stage buffers of BKS k-columns; loads run AHEAD stages ahead of
-// the MFMAs and stay in flight across the per-stage barrier (raw s_barrier + counted vmcnt: a
-// __syncthreads() would drain them, cdna_hip_programming.md §5 "Pipelining across barriers").
-// One wave-instruction moves 64 x 16 B = 1 KiB = one 128-row f64 column (two f32 columns),
-// written contiguously at a wave-uniform LDS base; columns (column pairs) are PAD apart.
-// Accumulator layout: acc[x][y][reg] = C(row = 64 wr + 16 y + lr, col = 32 wc + 16 x +
-// orow(lk, reg)) with w = wave, wr = w & 1, wc = w >> 1, lr = lane & 15, lk = lane >> 4.
+// One 512-thread workgroup (8 waves, v_mfma_f64_16x16x4f64 / v_mfma_f32_16x16x4f32) computes
+// acc = A B^T, A and B being 128-row column-major operand panels K deep.  Operands are staged by
+// LDS-DMA (global_load_lds_dwordx4, no VGPRs) into a ring of NBUF stage buffers of BK k-columns;
+// loads run AHEAD stages ahead of the MFMAs and stay in flight across the per-stage barrier (raw
+// s_barrier + counted vmcnt: a __syncthreads() would drain them).  One wave-instruction moves
+// 64 x 16 B = 1 KiB = one 128-row f64 column (two f32 columns), written contiguously at a
+// wave-uniform LDS base; columns (column pairs) are PAD apart.
+//
+// In order: the MFMA traits (Mfma), the stage depths and feed forms by precision (BkOf, FeedOf),
+// the LDS layout of a stage (Stage), the ring's shared pieces (lds_dma16, stage_issue, stage_wait:
+// the counted-vmcnt invariant is written there), then the products:
+//   tile_mma          128 x 128, the 8 waves 64 x 32 blocks each (wave_block): the update, SYRK
+//                     and pair-statistics product;
+//   tile_mma_trirows  128 x 128 for a lower-triangular B, each wave 16 rows (the TRSM task);
+//   tile_mma_rows16   16 x 128 (the narrow label-row update);
+//   tile_mma_tall     256 x 128, 64 x 64 blocks (stand-alone GEMMs and the paired updates);
+//   tile_mma2         two 128 x 128 products over adjacent column ranges in one ring pass.
+// tile_mma's accumulator layout: acc[x][y][reg] = C(row = 64 wr + 16 y + lr, col = 32 wc + 16 x +
+// orow(lk, reg)) with w = wave, (wr, wc) = wave_block(w), lr = lane & 15, lk = lane >> 4.
+//
+// Compile-time A/B switches for the ring depth, the f32 stage depth and the feed forms were
+// removed once their losers were measured (below and DESIGN.md §4.1); commit d50ea04 is the last
+// one that has them.
 #pragma once
 #include "gprx_internal.h"
 #include "k_handoff.h"
@@ -51,35 +65,23 @@ struct Mfma<float> {
     __device__ static inline int orow(int lk, int reg) { return 4 * lk + reg; }
 };
 
-// Operand staging: global_load_lds_dwordx4 (LDS-DMA, no VGPRs) into a ring of NBUF stage
-// buffers of BKS k-columns; loads run 3 stages ahead of the MFMAs and stay in flight across
-// the per-stage barrier (raw s_barrier + counted vmcnt: a __syncthreads() would drain them).
-// One wave-instruction moves 64 x 16 B = 1 KiB = one 128-row f64 column (two f32 columns),
-// written contiguously at a wave-uniform LDS base; columns (column pairs) are PAD apart.
-#ifndef GPRX_PT_BKS
-#define GPRX_PT_BKS 16
-#define GPRX_PT_NBUF 4
-#endif
-constexpr int BKS = GPRX_PT_BKS;
-constexpr int NBUF = GPRX_PT_NBUF;
+constexpr int BKS = 16;          // k-columns per f64 stage (and per pair-statistics stage)
+constexpr int NBUF = 4;          // stage buffers in the ring
 constexpr int AHEAD = NBUF - 1;  // stages in flight ahead of the one being computed
 // k-columns per stage of the factorisation's products by precision (the pair statistics keep
 // BKS: their feature widths are multiples of 16).  f32 stages are twice as deep (the f64
-// stage's LDS bytes, half the barriers per flop): C4's f32 factor 101.9 -> 98.6 ms, same-box
-// A/B (profiles/r04f); GPRX_F32_BKS=16 builds the round-3 depth
-// (GPRX_F32_BKS=64: two 139 KB ring buffers, one stage ahead -- probe 0.818 -> 0.836 of the f32
-// bound, C4's factor only 101.7 -> 100.9 ms same box, profiles/r05yz; not the default: one
-// stage of lead is thin for the sharded fit's window-fed operands)
-#ifndef GPRX_F32_BKS
-#define GPRX_F32_BKS 32
-#endif
+// stage's LDS bytes, half the barriers per flop): C4's f32 factor 101.9 -> 98.6 ms against the
+// round-3 depth of 16, same-box A/B (profiles/r04f).  (64-deep f32 stages, two 139 KB ring
+// buffers and one stage ahead: probe 0.818 -> 0.836 of the f32 bound, C4's factor only 101.7 ->
+// 100.9 ms same box, profiles/r05yz; not kept: one stage of lead is thin for the sharded fit's
+// window-fed operands.)
 template <typename T>
 struct BkOf {
     static constexpr int v = BKS;
 };
 template <>
 struct BkOf<float> {
-    static constexpr int v = GPRX_F32_BKS;
+    static constexpr int v = 32;
 };
 
 // tile_mma's operand feed by precision (scripts/mma_probe.hip decomposes the f64 stage: 4880
@@ -93,36 +95,19 @@ struct BkOf<float> {
 //         them -- lgkmcnt(0), with an LDS-DMA pending -- before the next step's first MFMA).
 // f64: late + mid 1 + spread refill (probe 0.839 -> 0.877 of the bound; C3 launch 26.45 ->
 // 25.71 ms and the C5 syrk 2.47 -> 2.39 ms per launch with mid 2, same box, profiles/r04s; mid 1
-// another 0.5% on both, r04ak); f32: all off
-// (late + mid 2 cost C4's factor 3%: 100.8 -> 103.6 ms, r04q).
-// GPRX_MMA_LATE / GPRX_MMA_MID / GPRX_MMA_SPREAD force a form for both (A/B builds).
-#ifndef GPRX_PAIR_FEED
-#define GPRX_PAIR_FEED 0
-#endif
-#ifndef GPRX_SHORT_FEED
-#define GPRX_SHORT_FEED -1
-#endif
+// another 0.5% on both, r04ak); f32: the early barrier, reads ahead of each step, refill in a
+// burst (late + mid 2 cost C4's factor 3%: 100.8 -> 103.6 ms, r04q).
 template <typename T>
 struct FeedOf {
-#ifdef GPRX_MMA_LATE
-    static constexpr bool late = GPRX_MMA_LATE != 0;
-#else
     static constexpr bool late = sizeof(T) == 8;
-#endif
-#ifdef GPRX_MMA_MID
-    static constexpr int mid = GPRX_MMA_MID;
-#else
     static constexpr int mid = sizeof(T) == 8 ? 1 : -1;
-#endif
     // late form: the refill's LDS-DMA issues one after each of the MFMAs that follow the
     // barrier, not in a burst after it (each issue holds its wave ~60 cycles; behind an MFMA
     // the pipe stays busy meanwhile): probe 0.860 -> 0.873, C3 launch 25.76 -> 25.71 ms
-#ifdef GPRX_MMA_SPREAD
-    static constexpr bool spread = GPRX_MMA_SPREAD != 0;
-#else
     static constexpr bool spread = sizeof(T) == 8;
-#endif
 };
+// tile_mma's FEED argument: the precision's form above, or the early form whatever the precision
+constexpr int FEED_OF_T = -1, FEED_EARLY = 0;
 
 template <typename T, int BK = BkOf<T>::v>
 struct Stage {
@@ -133,8 +118,6 @@ struct Stage {
     static constexpr int GRP = BK / CPI;         // instructions per operand per stage
     static constexpr int IPW = 2 * GRP / 8;      // instructions per wave per stage
     static constexpr int STG = 2 * GRP * SRP;    // elements per stage buffer (A slots, then B)
-    static constexpr int NB = BK > 32 ? 2 : NBUF;  // ring buffers (deeper stages: fewer of them)
-    static constexpr int AH = NB - 1;              // stages in flight ahead of the one computed
     // f32 (two columns per instruction): the second column of a pair is stored rotated by ROT
     // rows.  The fragment reads are ds_read_b32 (banks (a/4) mod 32, lanes 0-31 one group):
     // lanes with lk = 0 and lk = 1 read k-columns kr and kr + 1 of one pair, 128 words apart --
@@ -158,8 +141,7 @@ struct Stage {
 
 template <typename T>
 constexpr size_t gemm_lds() {  // (the larger of the two stage depths a launch may use)
-    return sizeof(T) * (Stage<T>::NB * Stage<T>::STG > NBUF * Stage<T, BKS>::STG ? Stage<T>::NB * Stage<T>::STG
-                                                                                  : NBUF * Stage<T, BKS>::STG);
+    return sizeof(T) * NBUF * (Stage<T>::STG > Stage<T, BKS>::STG ? Stage<T>::STG : Stage<T, BKS>::STG);
 }
 
 using ho::st_sc1;  // global_store ... sc1
@@ -167,6 +149,67 @@ using ho::st_sc1;  // global_store ... sc1
 template <int N>
 __device__ __forceinline__ void wait_vm() {
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// ------------------------------------------------------------------------------------------
+// The staging ring.  Stage st of a product (its k-columns st BK ..) lives in ring buffer
+// st % NBUF; the 8 waves share a stage's 2 GRP load instructions, IPW each.  A product primes the
+// ring with its first AHEAD stages, then per stage waits for it and meets the other waves
+// (stage_wait) and refills the buffer that the barrier has freed, so that AHEAD - 1 stages stay in
+// flight under the MFMAs.
+//
+// What is shared here is what hipcc compiles to the same instructions as the text it replaced
+// (`make codeobj-kernels` against commit d50ea04).  The fragment reads and k-step loops, and the
+// issue of tile_mma (its Bpan form and per-instruction spread), of the tall tile (three operand
+// groups) and of the predict kernel (k_pairs.hip: a stage index running across blocks) stay
+// written in their products: as shared inline functions they came out as different code for
+// every kernel that uses them (other block layout, up to 8 VGPRs more).
+// ------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ void lds_dma16(const T* src, T* dst) {  // 16 B per lane, global -> LDS
+    __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
+}
+
+// All of this wave's loads for stage st (k-columns st BK ..) of the operands A, B into the stage
+// buffer buf: instruction slot g is wave-uniform (A 0..GRP-1, B GRP..2GRP-1), each lane brings
+// 16 B of one column.
+template <typename T, int BK>
+__device__ __forceinline__ void stage_issue(const T* __restrict__ A, int64_t lda, const T* __restrict__ B, int64_t ldb,
+                                            int st, T* buf, const int t) {
+    typedef Stage<T, BK> S;
+    const int lane = t & 63, w = t >> 6;
+    const int lcol = lane / S::LPC, lrow = S::src_row(lane);
+#pragma unroll
+    for (int u = 0; u < S::IPW; u++) {
+        const int g = w * S::IPW + u;
+        const bool isB = g >= S::GRP;
+        const int gg = isB ? g - S::GRP : g;
+        const int64_t col = (int64_t)st * BK + gg * S::CPI + lcol;
+        const T* src = isB ? (B + lrow + col * ldb) : (A + lrow + col * lda);
+        lds_dma16(src, buf + g * S::SRP);
+    }
+}
+
+// Before a stage is computed: this wave's loads of it have landed while `ahead` (= stages - 1 -
+// stage) younger stages may stay in flight, and every wave's, and every wave is done reading the
+// stage before, whose buffer the caller refills next with stage + AHEAD.
+// vmcnt counts a wave's memory loads IN ORDER, and each stage is IPW of them per wave, so "all but
+// the youngest k stages" is vmcnt(k IPW); at most AHEAD - 1 = 2 stages are younger.  This holds
+// only while nothing else loads between the ring's issues: a load from anywhere else inside the
+// product joins the count and makes every later wait drain the ring (tile_mma's Bpan comment has
+// the price), and one issued before the product has to be waited for before the ring is primed
+// (the predict kernel).
+// (Reading the next stage's first fragments before this barrier, so the MFMAs start right after
+// it, measured +0.5% alone but cost 3% inside the factorisation: it shortens the load lead to two
+// stages.)
+template <int IPW, typename I>
+__device__ __forceinline__ void stage_wait(I ahead) {
+    static_assert(AHEAD == 3, "the ladder below: two stages younger at the most");
+    if (ahead >= 2) wait_vm<2 * IPW>();
+    else if (ahead >= 1) wait_vm<IPW>();
+    else wait_vm<0>();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
 }
 
 // Output block (wr, wc) of wave w (64 x 32 outputs at rows 64 wr, columns 32 wc).  Waves w and
@@ -202,9 +245,10 @@ __device__ __forceinline__ void wave_block(int w, int& wr, int& wc) {
 // ldb (the distributed factorisation's received tiles: one packed 128 x 128 tile per panel,
 // ldb = 128, each panel in its own receive buffer).
 // ACC: acc += A B^T (acc is not cleared: consecutive K ranges into one accumulator).
-// FEED: -1 the precision's form (FeedOf), 0 the early barrier with reads ahead of each step
-// (the pair statistics' K = 32..96 products: the late form made the stand-alone build 4% slower)
-template <typename T, int MAP = 0, bool ACC = false, int BK = BkOf<T>::v, int FEED = -1>
+// FEED: FEED_OF_T the precision's form (FeedOf), FEED_EARLY the early barrier with reads ahead of
+// each step (the pair statistics' K = 32..96 products: the late form made the stand-alone build 4%
+// slower)
+template <typename T, int MAP = 0, bool ACC = false, int BK = BkOf<T>::v, int FEED = FEED_OF_T>
 __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], const T* __restrict__ A, int64_t lda,
                                          const T* __restrict__ B, int64_t ldb, int K, int kact, T* smem,
                                          const int t, const uint64_t* Bpan = nullptr) {
@@ -229,7 +273,7 @@ __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], c
     }
 
     auto issue_u = [&](int st, int u) {
-        T* buf = smem + (st % S::NB) * S::STG;
+        T* buf = smem + (st % NBUF) * S::STG;
         {
             const int g = w * S::IPW + u;  // wave-uniform slot: A 0..GRP-1, B GRP..2GRP-1
             const bool isB = g >= S::GRP;
@@ -246,8 +290,7 @@ __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], c
             } else {
                 src = isB ? (B + lrow + col * ldb) : (A + lrow + col * lda);
             }
-            __builtin_amdgcn_global_load_lds((const void*)src,
-                                             (__attribute__((address_space(3))) void*)(buf + g * S::SRP), 16, 0, 0);
+            lds_dma16(src, buf + g * S::SRP);
         }
     };
     auto issue = [&](int st) {
@@ -264,21 +307,11 @@ __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], c
 
     const int nst = K / BK;
 #pragma unroll
-    for (int p = 0; p < S::AH; p++)
+    for (int p = 0; p < AHEAD; p++)
         if (p < nst) issue(p);
-    // this wave's loads of stage st have landed (later stages may stay in flight), and every
-    // wave's, and every wave is done reading the buffer refilled next; then the refill
     auto stage_sync = [&](int st) {
-        const int ahead = nst - 1 - st;
-        if (S::AH >= 3 && ahead >= 2) wait_vm<(S::AH >= 3 ? 2 : 0) * S::IPW>();
-        else if (S::AH >= 2 && ahead >= 1) wait_vm<S::IPW>();
-        else wait_vm<0>();
-        // (Reading the next stage's first fragments before this barrier, so the MFMAs start
-        // right after it, measured +0.5% alone but cost 3% inside the factorisation: it
-        // shortens the load lead to two stages.)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (st + S::AH < nst) issue(st + S::AH);
+        stage_wait<S::IPW>(nst - 1 - st);
+        if (st + AHEAD < nst) issue(st + AHEAD);
     };
     // The MFMA stages and the idle ones (above the diagonal of a diagonal tile, beyond the
     // triangle of a triangular B) are loops of their own with the same barriers: with a
@@ -286,25 +319,28 @@ __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], c
     // (64 register moves, and a wait for the last MFMAs, per stage).
     // (rounded up: kact = 32 (wc + 1) for a triangular B, whose columns beyond it are stored zeros)
     const int nmf = (__builtin_amdgcn_readfirstlane(kact < K ? kact : K) + BK - 1) / BK;
-    constexpr bool LATE = FEED < 0 && FeedOf<T>::late;
-    constexpr int MID = FEED < 0 ? FeedOf<T>::mid : -1;
+    constexpr bool LATE = FEED == FEED_OF_T && FeedOf<T>::late;
+    static_assert(LATE || FEED == FEED_EARLY || FeedOf<T>::mid < 0, "early barrier: reads ahead of each step");
     if constexpr (LATE) {
+        constexpr int MID = FeedOf<T>::mid;
         // late barrier B_st inside stage st's last k-step (after MID of its MFMAs): stage
         // st + 1 has landed for every wave and every wave is past stage st - 1, whose buffer takes
-        // stage st + AH; stage st + 1's first fragments are read right after it, under the rest of
+        // stage st + AHEAD; stage st + 1's first fragments are read right after it, under the rest of
         // stage st's MFMAs
-        static_assert(S::AH >= 2 && MID >= 0, "late barrier: two stages ahead, mid-step reads");
+        static_assert(MID >= 0, "late barrier: mid-step reads");
         constexpr bool SPREAD = FeedOf<T>::spread;
         static_assert(!SPREAD || MID + S::IPW < 8, "spread refill: a DMA behind each MFMA after the barrier");
+        // (stage_wait's ladder one stage on: stage st + 1 must have landed, and only stage st + 2
+        // can be younger; no lgkmcnt wait, the reads around it are pinned)
         auto late_sync = [&](int st, bool refill) {
-            if (S::AH >= 3 && nst - 2 - st >= 1) wait_vm<(S::AH >= 3 ? 1 : 0) * S::IPW>();
+            if (nst - 2 - st >= 1) wait_vm<S::IPW>();
             else wait_vm<0>();
             __builtin_amdgcn_s_barrier();
-            if (refill && st + S::AH < nst) issue(st + S::AH);
+            if (refill && st + AHEAD < nst) issue(st + AHEAD);
         };
         if (nst > 0) {  // stage 0 visible
-            if (S::AH >= 3 && nst >= 3) wait_vm<(S::AH >= 3 ? 2 : 0) * S::IPW>();
-            else if (S::AH >= 2 && nst >= 2) wait_vm<S::IPW>();
+            if (nst >= 3) wait_vm<2 * S::IPW>();
+            else if (nst >= 2) wait_vm<S::IPW>();
             else wait_vm<0>();
             __builtin_amdgcn_s_barrier();
         }
@@ -313,8 +349,8 @@ __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], c
             const T* b0 = smem + S::GRP * S::SRP;
             T fa[2][4], fb[2][2];
             auto frag = [&](int st, int kq, int r) {
-                const T* a = a0 + (st % S::NB) * S::STG;
-                const T* b = b0 + (st % S::NB) * S::STG;
+                const T* a = a0 + (st % NBUF) * S::STG;
+                const T* b = b0 + (st % NBUF) * S::STG;
                 const int kr = kq * 4 + lk;
 #pragma unroll
                 for (int x = 0; x < 2; x++) fb[r][x] = b[S::at(kr, wc * 32 + x * 16 + lr)];
@@ -347,7 +383,7 @@ __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], c
                                 acc[x][y] = Tr::mma(fb[kq & 1][x], fa[kq & 1][y], acc[x][y]);
                             if (SPREAD && kq == KQ - 1 && m > MID && m - MID - 1 < S::IPW) {
                                 __builtin_amdgcn_sched_barrier(0);
-                                if (st + S::AH < nst) issue_u(st + S::AH, m - MID - 1);
+                                if (st + AHEAD < nst) issue_u(st + AHEAD, m - MID - 1);
                                 __builtin_amdgcn_sched_barrier(0);
                             }
                             m++;
@@ -366,8 +402,8 @@ __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], c
             for (int st = 0; st < nmf; st++) {
                 stage_sync(st);
                 // fragments of step kq+1 are read while the MFMAs of step kq run
-                const T* a = a0 + (st % S::NB) * S::STG;
-                const T* b = b0 + (st % S::NB) * S::STG;
+                const T* a = a0 + (st % NBUF) * S::STG;
+                const T* b = b0 + (st % NBUF) * S::STG;
                 T fa[2][4], fb[2][2];
                 auto frag = [&](int kq, int r) {
                     const int kr = kq * 4 + lk;
@@ -418,37 +454,16 @@ __device__ __forceinline__ void tile_mma(typename Mfma<T>::acc_t (&acc)[2][4], c
                     continue;
                 }
                 frag(0, 0);
-                if constexpr (MID < 0) {
 #pragma unroll
-                    for (int kq = 0; kq < BK / 4; kq++) {
-                        if (kq + 1 < BK / 4) frag(kq + 1, (kq + 1) & 1);
-                        __builtin_amdgcn_sched_barrier(0);  // keep those reads ahead of these MFMAs
+                for (int kq = 0; kq < BK / 4; kq++) {
+                    if (kq + 1 < BK / 4) frag(kq + 1, (kq + 1) & 1);
+                    __builtin_amdgcn_sched_barrier(0);  // keep those reads ahead of these MFMAs
 #pragma unroll
-                        for (int x = 0; x < 2; x++)
+                    for (int x = 0; x < 2; x++)
 #pragma unroll
-                            for (int y = 0; y < 4; y++)
-                                if (MAP != 2 || 4 * wr + y >= 2 * wc + x)  // (MAP 2: wave-uniform tile skip)
-                                    acc[x][y] = Tr::mma(fb[kq & 1][x], fa[kq & 1][y], acc[x][y]);
-                    }
-                } else {
-                    // step kq+1's fragment reads pinned after the first MID MFMAs of step kq
-#pragma unroll
-                    for (int kq = 0; kq < BK / 4; kq++) {
-                        int m = 0;
-#pragma unroll
-                        for (int x = 0; x < 2; x++)
-#pragma unroll
-                            for (int y = 0; y < 4; y++) {
-                                if (m == MID) {
-                                    __builtin_amdgcn_sched_barrier(0);
-                                    if (kq + 1 < BK / 4) frag(kq + 1, (kq + 1) & 1);
-                                    __builtin_amdgcn_sched_barrier(0);
-                                }
-                                if (MAP != 2 || 4 * wr + y >= 2 * wc + x)  // (MAP 2: wave-uniform tile skip)
-                                    acc[x][y] = Tr::mma(fb[kq & 1][x], fa[kq & 1][y], acc[x][y]);
-                                m++;
-                            }
-                    }
+                        for (int y = 0; y < 4; y++)
+                            if (MAP != 2 || 4 * wr + y >= 2 * wc + x)  // (MAP 2: wave-uniform tile skip)
+                                acc[x][y] = Tr::mma(fb[kq & 1][x], fa[kq & 1][y], acc[x][y]);
                 }
             }
             st0 = nmf;
@@ -480,38 +495,20 @@ __device__ __forceinline__ void tile_mma_trirows(typename Mfma<T>::acc_t (&acc)[
     constexpr int NST = GT / BK;
     const int lane = t & 63, w = t >> 6;
     const int lr = lane & 15, lk = lane >> 4;
-    const int lcol = lane / S::LPC, lrow = S::src_row(lane);
-    auto issue = [&](int st) {
-        T* buf = smem + (st % S::NB) * S::STG;
-#pragma unroll
-        for (int u = 0; u < S::IPW; u++) {
-            const int g = w * S::IPW + u;
-            const bool isB = g >= S::GRP;
-            const int gg = isB ? g - S::GRP : g;
-            const int64_t col = (int64_t)st * BK + gg * S::CPI + lcol;
-            const T* src = isB ? (B + lrow + col * ldb) : (A + lrow + col * lda);
-            __builtin_amdgcn_global_load_lds((const void*)src,
-                                             (__attribute__((address_space(3))) void*)(buf + g * S::SRP), 16, 0, 0);
-        }
-    };
+    auto issue = [&](int st) { stage_issue<T, BK>(A, lda, B, ldb, st, smem + (st % NBUF) * S::STG, t); };
 #pragma unroll
     for (int x = 0; x < 2; x++)
 #pragma unroll
         for (int y = 0; y < 4; y++) acc[x][y] = acc_t{0};
 #pragma unroll
-    for (int p = 0; p < S::AH; p++)
+    for (int p = 0; p < AHEAD; p++)
         if (p < NST) issue(p);
     auto stage = [&](auto stc) {
         constexpr int st = decltype(stc)::value;
-        constexpr int ahead = NST - 1 - st;
-        if constexpr (S::AH >= 3 && ahead >= 2) wait_vm<2 * S::IPW>();
-        else if constexpr (S::AH >= 2 && ahead >= 1) wait_vm<S::IPW>();
-        else wait_vm<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if constexpr (st + S::AH < NST) issue(st + S::AH);
+        stage_wait<S::IPW>(NST - 1 - st);
+        if constexpr (st + AHEAD < NST) issue(st + AHEAD);
         constexpr int G0 = (st * BK) / 16;  // first live column group
-        const T* a = smem + (st % S::NB) * S::STG;
+        const T* a = smem + (st % NBUF) * S::STG;
         const T* b = a + S::GRP * S::SRP;
         T fa[2], fb[2][8];
         auto frag = [&](int kq, int r) {
@@ -559,35 +556,17 @@ __device__ __forceinline__ void tile_mma_rows16(typename Mfma<T>::acc_t& acc, co
     typedef Stage<T, BK> S;
     const int lane = t & 63, w = t >> 6;
     const int lr = lane & 15, lk = lane >> 4;
-    const int lcol = lane / S::LPC, lrow = S::src_row(lane);
-    auto issue = [&](int st) {
-        T* buf = smem + (st % S::NB) * S::STG;
-#pragma unroll
-        for (int u = 0; u < S::IPW; u++) {
-            const int g = w * S::IPW + u;
-            const bool isB = g >= S::GRP;
-            const int gg = isB ? g - S::GRP : g;
-            const int64_t col = (int64_t)st * BK + gg * S::CPI + lcol;
-            const T* src = isB ? (B + lrow + col * ldb) : (A + lrow + col * lda);
-            __builtin_amdgcn_global_load_lds((const void*)src,
-                                             (__attribute__((address_space(3))) void*)(buf + g * S::SRP), 16, 0, 0);
-        }
-    };
+    auto issue = [&](int st) { stage_issue<T, BK>(A, lda, B, ldb, st, smem + (st % NBUF) * S::STG, t); };
     acc = acc_t{0};
     const int nst = __builtin_amdgcn_readfirstlane(K) / BK;
 #pragma unroll
-    for (int p = 0; p < S::AH; p++)
+    for (int p = 0; p < AHEAD; p++)
         if (p < nst) issue(p);
 #pragma nounroll
     for (int st = 0; st < nst; st++) {
-        const int ahead = nst - 1 - st;
-        if (S::AH >= 3 && ahead >= 2) wait_vm<(S::AH >= 3 ? 2 : 0) * S::IPW>();
-        else if (S::AH >= 2 && ahead >= 1) wait_vm<S::IPW>();
-        else wait_vm<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (st + S::AH < nst) issue(st + S::AH);
-        const T* a = smem + (st % S::NB) * S::STG;
+        stage_wait<S::IPW>(nst - 1 - st);
+        if (st + AHEAD < nst) issue(st + AHEAD);
+        const T* a = smem + (st % NBUF) * S::STG;
         const T* b = a + S::GRP * S::SRP;
         constexpr bool PAIRED = sizeof(T) == 4 && BK >= 32 && S::CPI == 2 && S::ROT == 0;
         if constexpr (PAIRED) {  // (tile_mma: k-step 2 j + h takes the k-columns 2 (4 j + lk) + h)
@@ -656,9 +635,7 @@ __device__ __forceinline__ void tile_mma_tall(typename Mfma<T>::acc_t (&acc)[4][
         for (int u = 0; u < IPW3; u++) {
             const int g = w * IPW3 + u, op = g / S::GRP, gg = g - op * S::GRP;  // op 0, 1: A halves, 2: B
             const int64_t col = (int64_t)st * BK + gg * S::CPI + lcol;
-            const T* src = (op == 2) ? (B + lrow + col * ldb) : (A + (int64_t)op * GT + lrow + col * lda);
-            __builtin_amdgcn_global_load_lds((const void*)src,
-                                             (__attribute__((address_space(3))) void*)(buf + g * S::SRP), 16, 0, 0);
+            lds_dma16((op == 2) ? (B + lrow + col * ldb) : (A + (int64_t)op * GT + lrow + col * lda), buf + g * S::SRP);
         }
     };
 #pragma unroll
@@ -694,14 +671,14 @@ __device__ __forceinline__ void tile_mma_tall(typename Mfma<T>::acc_t (&acc)[4][
     // SPREAD (f64, FeedOf::spread): the next stage's DMAs go out one behind each of the stage's
     // first MFMAs instead of in a burst after the barrier, which held both waves of a SIMD (~60
     // cycles an instruction) while its MFMA pipe idled
+    // (issue_u is issue's loop body once more: issue written as a loop over it compiles to other
+    // code for every tall kernel)
     constexpr bool SPREAD = FeedOf<T>::spread && MID + IPW3 + 1 <= 16;
     auto issue_u = [&](int st, int u) {
         T* buf = smem + (st & 1) * STG3;
         const int g = w * IPW3 + u, op = g / S::GRP, gg = g - op * S::GRP;
         const int64_t col = (int64_t)st * BK + gg * S::CPI + lcol;
-        const T* src = (op == 2) ? (B + lrow + col * ldb) : (A + (int64_t)op * GT + lrow + col * lda);
-        __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(buf + g * S::SRP),
-                                         16, 0, 0);
+        lds_dma16((op == 2) ? (B + lrow + col * ldb) : (A + (int64_t)op * GT + lrow + col * lda), buf + g * S::SRP);
     };
     auto stage = [&](int st, auto cp) {
         constexpr int CP = decltype(cp)::value;
@@ -784,25 +761,6 @@ __device__ __forceinline__ void tile_mma_tall(typename Mfma<T>::acc_t (&acc)[4][
 // and a barrier between them; the pair statistics of a periodic + r2 tree are such a pair
 // (k_pairs.h: the r2 and periodic feature columns are adjacent).  Every wave multiplies.
 template <typename T>
-__device__ __forceinline__ void ring_issue(const T* __restrict__ A, int64_t lda, const T* __restrict__ B, int64_t ldb,
-                                           int st, T* smem, const int t) {
-    typedef Stage<T, BKS> S;
-    const int lane = t & 63, w = t >> 6;
-    const int lcol = lane / S::LPC, lrow = S::src_row(lane);
-    T* buf = smem + (st % NBUF) * S::STG;
-#pragma unroll
-    for (int u = 0; u < S::IPW; u++) {
-        const int g = w * S::IPW + u;
-        const bool isB = g >= S::GRP;
-        const int gg = isB ? g - S::GRP : g;
-        const int64_t col = (int64_t)st * BKS + gg * S::CPI + lcol;
-        const T* src = isB ? (B + lrow + col * ldb) : (A + lrow + col * lda);
-        __builtin_amdgcn_global_load_lds((const void*)src, (__attribute__((address_space(3))) void*)(buf + g * S::SRP),
-                                         16, 0, 0);
-    }
-}
-
-template <typename T>
 __device__ __forceinline__ void tile_mma2(typename Mfma<T>::acc_t (&acc1)[2][4], typename Mfma<T>::acc_t (&acc2)[2][4],
                                           const T* __restrict__ A, int64_t lda, const T* __restrict__ B, int64_t ldb,
                                           int K1, int K2, T* smem, const int t) {
@@ -812,7 +770,7 @@ __device__ __forceinline__ void tile_mma2(typename Mfma<T>::acc_t (&acc1)[2][4],
     const int lane = t & 63, w = t >> 6;
     const int wr = w & 1, wc = w >> 1;
     const int lr = lane & 15, lk = lane >> 4;
-    auto issue = [&](int st) { ring_issue<T>(A, lda, B, ldb, st, smem, t); };
+    auto issue = [&](int st) { stage_issue<T, BKS>(A, lda, B, ldb, st, smem + (st % NBUF) * S::STG, t); };
 #pragma unroll
     for (int x = 0; x < 2; x++)
 #pragma unroll
@@ -826,12 +784,7 @@ __device__ __forceinline__ void tile_mma2(typename Mfma<T>::acc_t (&acc1)[2][4],
     for (int p = 0; p < AHEAD; p++)
         if (p < nst) issue(p);
     auto stage_sync = [&](int st) {
-        const int ahead = nst - 1 - st;
-        if (AHEAD >= 3 && ahead >= 2) wait_vm<(AHEAD >= 3 ? 2 : 0) * S::IPW>();
-        else if (AHEAD >= 2 && ahead >= 1) wait_vm<S::IPW>();
-        else wait_vm<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        stage_wait<S::IPW>(nst - 1 - st);
         if (st + AHEAD < nst) issue(st + AHEAD);
     };
     const T* a0 = smem;

@@ -207,8 +207,7 @@ __device__ __forceinline__ void predict_mma_body(const KCanon<T>* __restrict__ K
             const int gg = isB ? g - S::GRP : g;
             const int64_t col = (int64_t)sx * BKS + gg * S::CPI + lcol;
             const T* src = isB ? (B + lrow + col * nfv) : (A + lrow + col * nfu);
-            __builtin_amdgcn_global_load_lds((const void*)src,
-                                             (__attribute__((address_space(3))) void*)(buf + g * S::SRP), 16, 0, 0);
+            lds_dma16(src, buf + g * S::SRP);
         }
     };
     auto load_block_consts = [&](int jb) {  // norms / alpha of block jb into parity jb & 1
@@ -224,12 +223,7 @@ __device__ __forceinline__ void predict_mma_body(const KCanon<T>* __restrict__ K
     for (int p = 0; p < AHEAD; p++)
         if (p < total) issue(p);
     auto stage_sync = [&](int64_t gs) {
-        const int64_t ahead = total - 1 - gs;
-        if (AHEAD >= 3 && ahead >= 2) wait_vm<(AHEAD >= 3 ? 2 : 0) * S::IPW>();
-        else if (AHEAD >= 2 && ahead >= 1) wait_vm<S::IPW>();
-        else wait_vm<0>();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
+        stage_wait<S::IPW>(total - 1 - gs);
         if (gs + AHEAD < total) issue(gs + AHEAD);
     };
     auto stages = [&](acc_t(&acc)[2][4], int64_t gbeg, int64_t gend) {
@@ -465,7 +459,7 @@ __device__ __forceinline__ void grad_mma_body(const KCanon<T>* __restrict__ Kd, 
     __syncthreads();
     typename Tr::acc_t ar[2][4];
     if (R2) {
-        tile_mma<T, 0, false, BKS, GPRX_PAIR_FEED>(ar, FU + i0, nf, FV + j0, nv_, Kr, Kr, smem, t);
+        tile_mma<T, 0, false, BKS, FEED_EARLY>(ar, FU + i0, nf, FV + j0, nv_, Kr, Kr, smem, t);
         load_weights();
         T nu[4];
 #pragma unroll
@@ -553,7 +547,7 @@ __device__ __forceinline__ void grad_mma_body(const KCanon<T>* __restrict__ Kd, 
         const KLeaf<T>& L = Kd->leaf[lp];
         const T sc = L.p[0], sig = L.p[2], c1 = L.c1;
         if (R2) __syncthreads();  // the staging ring is reused
-        tile_mma<T, 0, false, BKS, GPRX_PAIR_FEED>(ar, FU + (int64_t)Kr * nf + i0, nf, FV + (int64_t)Kr * nv_ + j0, nv_, Kp, Kp, smem, t);
+        tile_mma<T, 0, false, BKS, FEED_EARLY>(ar, FU + (int64_t)Kr * nf + i0, nf, FV + (int64_t)Kr * nv_ + j0, nv_, Kp, Kp, smem, t);
         load_weights();
         double a0 = 0, a2 = 0;
         each([&](auto cc) {
@@ -573,7 +567,7 @@ __device__ __forceinline__ void grad_mma_body(const KCanon<T>* __restrict__ Kd, 
         });
         __syncthreads();
         typename Tr::acc_t af[2][4];
-        tile_mma<T, 0, false, BKS, GPRX_PAIR_FEED>(af, GU + i0, nf, GV + j0, nv_, Kf, Kf, smem, t);
+        tile_mma<T, 0, false, BKS, FEED_EARLY>(af, GU + i0, nf, GV + j0, nv_, Kf, Kf, smem, t);
         double a1 = 0;
         each([&](auto cc) {
             constexpr int x = decltype(cc)::value >> 2, reg = decltype(cc)::value & 3;

@@ -31,7 +31,7 @@ using ho::wave_id;
 // ------------------------------------------------------------------------------------------
 // Bpan: B by 128-column panels (tile_mma): the distributed factorisation's window tiles.
 // MAP: the wave -> output-block map (k_mma.h wave_block): 1 for triangular B, 2 for lower.
-template <typename T, bool UPDATE, int MAP = 0, int FEED = -1>
+template <typename T, bool UPDATE, int MAP = 0>
 __device__ __forceinline__ void tile_gemm(T* __restrict__ C, int64_t ldc, const T* __restrict__ A, int64_t lda,
                                           const T* __restrict__ B, int64_t ldb, int K, bool lower, T* smem,
                                           const int t, bool tri = false, const uint64_t* Bpan = nullptr) {
@@ -58,8 +58,7 @@ __device__ __forceinline__ void tile_gemm(T* __restrict__ C, int64_t ldc, const 
             }
     }
     acc_t acc[2][4];
-    tile_mma<T, MAP, false, BkOf<T>::v, FEED>(acc, A, lda, B, ldb, K, !active ? 0 : (tri ? 32 * (wc + 1) : K), smem, t,
-                                           Bpan);
+    tile_mma<T, MAP>(acc, A, lda, B, ldb, K, !active ? 0 : (tri ? 32 * (wc + 1) : K), smem, t, Bpan);
     if (!active) return;
 #pragma unroll
     for (int x = 0; x < 2; x++) {

@@ -457,7 +457,7 @@ __global__ __launch_bounds__(NT) void potrf_tiles_kernel(Args<T> a) {
                 } else if (k > 0) {
                     tile_trsm<T>(Akm, DB, Akm, DB, a.Linv + (int64_t)(k - 1) * DB * DB, DB, smem, tid);
                     publish(a.lcnt + k, k, false);
-                    tile_gemm<T, true, 2, GPRX_SHORT_FEED>(Akk, DB, Akm, DB, Akm, DB, GT, true, smem, tid);
+                    tile_gemm<T, true, 2>(Akk, DB, Akm, DB, Akm, DB, GT, true, smem, tid);
                     local_sync();
                 }
                 diag_factor<T>(Akk, DB, a.Linv + (int64_t)k * DB * DB, a.info, (int64_t)k * DB, smem_raw, tid, a.dbg,
@@ -550,7 +550,7 @@ __global__ __launch_bounds__(NT) void potrf_tiles_kernel(Args<T> a) {
                 if (a.trace) dt[0] = wall_clock64();
                 publish(a.lcnt + k, k, false);  // L_{k,k-1} final: unblocks the updates of column k
                 if (a.trace) dt[1] = wall_clock64();
-                tile_gemm<T, true, 2, GPRX_SHORT_FEED>(Akk, ld, Akm, ld, Akm, ld, GT, true, smem, tid);
+                tile_gemm<T, true, 2>(Akk, ld, Akm, ld, Akm, ld, GT, true, smem, tid);
                 local_sync();
             }
             if (a.trace) dt[2] = wall_clock64();

@@ -108,7 +108,7 @@ for step in "$@"; do
     diag)
         timeout -k 10 120 python scripts/diag_bench.py > "$O/diag_bench.json" 2> "$O/diag_bench.err" || fail diag $? "$O/diag_bench.err"
         ;;
-    probe)  # the tile mainloop alone per operand-feed variant (tools/probe/mma_probe*, built from scripts/mma_probe.hip)
+    probe)  # the tile mainloop alone, every binary under tools/probe/ (mma_probe*, built from scripts/mma_probe.hip)
         for f in tools/probe/mma_probe*; do
             for dt in f32 f64; do
                 for mode in 0 1; do

@@ -78,7 +78,7 @@ int run(int K, int reps, int mode) {
     const double flops = 2.0 * 128 * 128 * K * reps * ncu;
     printf("{\"dtype\": \"%s\", \"K\": %d, \"reps\": %d, \"mode\": %d, \"BK\": %d, \"NB\": %d, "
            "\"cycles_per_stage\": %.0f, \"mfma_bound_frac\": %.4f, \"tflops\": %.2f, \"ghz\": %.3f}\n",
-           sizeof(T) == 8 ? "f64" : "f32", K, reps, mode, BK, Stage<T>::NB, avg / stages,
+           sizeof(T) == 8 ? "f64" : "f32", K, reps, mode, BK, NBUF, avg / stages,
            bound / (avg / stages), flops / (best * 1e9), avg / (best * 1e6));
     hipFree(M);
     hipFree(out);
