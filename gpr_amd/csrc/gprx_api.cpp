@@ -302,6 +302,15 @@ gprx_status gprx_model_lml(gprx_model* M, uint32_t flags, double* value, double*
     });
 }
 
+gprx_status gprx_model_loo(gprx_model* M, uint32_t flags, double* value, void* mean, void* var, double* grad,
+                           int32_t* nparams) {
+    return model_call(M, true, "gprx_model_loo: NULL model", CALL_PROF | CALL_DEVICE, [&] {
+        GPRX_REQUIRE(M->fitted || (M->has_data && M->has_kernel), GPRX_ERR_STATE,
+                     "gprx_model_loo: set the data, the kernel and the noise first");
+        return by_dtype(M->dt, [&](auto t) { return model_loo<decltype(t)>(M, flags, value, mean, var, grad, nparams); });
+    });
+}
+
 gprx_status gprx_model_set_sparse_cov(gprx_model* M, const void* W) {
     return model_call(M, W, "gprx_model_set_sparse_cov: NULL argument", 0, [&] {
         GPRX_REQUIRE(M->has_data && M->has_kernel && !M->host_k, GPRX_ERR_STATE,

@@ -562,6 +562,12 @@ void launch_lml_grad_mma(const KCanon<T>& K, const KCanon<T>* Kd, const T* X, in
                          const T* FV, T* GU, T* GV, int64_t nf, const T* alpha, const T* C, int64_t ldc, double* part,
                          double* acc, hipStream_t s,
                          const uint64_t* ctab = nullptr);  // ctab: C tile (i, j) pointers of a sharded fit (gprx_dist.cpp)
+// The same pass with the two-vector symmetric weights w_ij = (alpha_i beta_j + alpha_j beta_i) / 2
+// - C_ij (x2 off the diagonal): the leave-one-out gradient (k_loo.hip)
+template <typename T>
+void launch_loo_grad_mma(const KCanon<T>& K, const KCanon<T>* Kd, const T* X, int64_t n, int d, const T* FU,
+                         const T* FV, T* GU, T* GV, int64_t nf, const T* alpha, const T* beta, const T* C, int64_t ldc,
+                         double* part, double* acc, hipStream_t s);
 // Rectangular form for the sparse likelihood (k_pairs.hip): acc[3 l + q] = sum over the
 // na x nb pairs (xa_i, xb_j) of (a_i b_j - C_ij) d leaf_l / d p_q.
 template <typename T>
@@ -762,7 +768,32 @@ template <typename T>
 void launch_spd_inverse_from_factor(const T* A, int64_t ldA, int64_t np, const T* Linv, T* V, T* C, hipStream_t s);
 template <typename T>
 void launch_lml_grad(const KCanon<T>& K, const T* X, const T* tab, int64_t n, int d, const T* alpha, const T* C,
-                     int64_t ldc, double* acc /* MAX_LEAF*3 */, hipStream_t s);
+                     int64_t ldc, double* acc /* MAX_LEAF*3 */, hipStream_t s,
+                     const T* beta = nullptr);  // two-vector symmetric weights, as launch_loo_grad_mma
+// V = L^{-T} alone (upper, ld np), the first half of launch_spd_inverse_from_factor
+template <typename T>
+void launch_factor_inverse_t(const T* A, int64_t ldA, int64_t np, const T* Linv, T* V, hipStream_t s);
+
+// ---- leave-one-out cross-validation (k_loo.hip) -----------------------------------------
+// doubles of the column-chunk partials launch_loo_diag and launch_loo_weights reduce through
+int64_t loo_part_elems(int64_t np);
+// part <- the column-chunk partials of c_i = sum_{k >= i} V[i + k np]^2 = diag(V V^T), V upper
+// (np x np, ld np, np a multiple of 128); launch_loo_vectors adds them up
+template <typename T>
+void launch_loo_diag(const T* V, int64_t np, double* part, hipStream_t s);
+// From alpha, Y (n x m, row-major) and c (cpart: launch_loo_diag's partials; nullptr: the diagonal
+// of C, ldc): mean = Y - alpha / c (n x m), var = 1 / c (n), value[0] = the sum over samples and
+// columns of log c / 2 - alpha^2 / (2 c) - log(2 pi) / 2 (vpart: ceil(np / 256) doubles of scratch).
+// u != nullptr (m = 1, the gradient's vectors, np long, zero from n on): u = alpha / c,
+// sw = sqrt(w), w = (1 + alpha^2 / c) / c, r = u / sw.
+template <typename T>
+void launch_loo_vectors(const T* alpha, const T* Y, int64_t n, int64_t np, int m, const double* cpart, const T* C,
+                        int64_t ldc, T* mean, T* var, T* u, T* sw, T* r, double* vpart, double* value, hipStream_t s);
+// B = sym(C) diag(sw) (the full np x np square, ld np, from the lower triangle of C) and
+// a = sym(C) u = B r (np long); part: loo_part_elems(np) doubles
+template <typename T>
+void launch_loo_weights(const T* C, int64_t ldc, int64_t np, const T* sw, const T* r, T* B, double* part, T* a,
+                        hipStream_t s);
 template <typename T>
 void launch_set_identity_pad(T* A, int64_t ld, int64_t n, int64_t np, hipStream_t s);
 template <typename T>

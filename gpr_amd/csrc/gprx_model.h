@@ -157,6 +157,11 @@ inline bool env_predict_direct() {
     static const bool direct = env_is("GPRX_PREDICT", "direct");
     return direct;
 }
+// GPRX_LML_GRAD=direct keeps the LML and leave-one-out gradients on the VALU kernel
+inline bool env_lml_grad_direct() {
+    static const bool direct = env_is("GPRX_LML_GRAD", "direct");
+    return direct;
+}
 
 }  // namespace gprx
 
@@ -203,6 +208,10 @@ struct gprx_model {
     // (swapped with A, Linv, X, Y when the status words are back, so a sliding window alternates
     // between the two sets) and the rotations' (c, s) pairs (k_remove.hip)
     gprx::DevBuf rmA, rmLinv, rmX, rmY, rmPairs;
+    // gprx_model_loo workspace: the gradient's vectors (u, sqrt w, u / sqrt w, a), the reductions'
+    // partials, the results on their way to the host and H / 2 (np x np; the call also writes B
+    // into V, which nothing reads once C exists)
+    gprx::DevBuf looVec, looPart, looOut, looH;
     // a fit (a refit, an append, or the fit inside an LML call) and new data free the posterior
     // workspace when it is large (one big variance call must not leave too little HBM
     // for the next fit on the device); the LML's own gradient pass does not
@@ -212,6 +221,7 @@ struct gprx_model {
             pvRb.release();
             pvFq.release();
         }
+        if (looH.bytes > (size_t(1) << 30)) looH.release();
     }
     // the kernel trees on the device (uploaded when they change): the model's T tree, and an fp32
     // model's double tree (the refinement's)
@@ -271,6 +281,8 @@ struct gprx_model {
     //                      buffers); full refit: fit, then as fit
     //   lml               as its fit                             as its fit, + inverse_done() on a
     //                                                             sharded fit
+    //   loo               fitted by Cholesky: nothing; else as   fitted: inverse_done() once a gradient
+    //                     its fit (no LU fallback)                  formed C; else as its fit
     //   (first dense use of a sharded fit: dense_gathered())
     //
     // "fit" = fitted, has_alpha, inv_ready.  set_data, set_kernel, set_kernel_matrix and set_noise
@@ -505,6 +517,9 @@ template <typename T>
 gprx_status model_core_matrix(gprx_model* M, void* Cout);
 template <typename T>
 gprx_status model_lml(gprx_model* M, uint32_t flags, double* value, double* grad, int32_t* nparams, double* logdet);
+template <typename T>
+gprx_status model_loo(gprx_model* M, uint32_t flags, double* value, void* mean, void* var, double* grad,
+                      int32_t* nparams);
 template <typename T>
 gprx_status model_predict_kx(gprx_model* M, const void* Kx, const void* Xq, int64_t q, void* mean, void* deriv);
 template <typename T>

@@ -1,5 +1,6 @@
 // gprx_query.cpp — what reads a fitted model: predict, the posterior covariance (dense, LU, sharded,
-// sparse), the core matrix, the log marginal likelihood and the caller-evaluated-kernel forms.
+// sparse), the core matrix, the log marginal likelihood, the leave-one-out cross-validation and the
+// caller-evaluated-kernel forms.
 #include "gprx_model.h"
 
 namespace gprx {
@@ -383,10 +384,8 @@ gprx_status model_lml(gprx_model* M, uint32_t flags, double* value, double* grad
         }
         M->grad.ensure(sizeof(double) * MAX_LEAF * 3);
         GPRX_HIP(hipMemsetAsync(M->grad.p, 0, sizeof(double) * MAX_LEAF * 3, s));
-        static const bool direct_grad =
-            std::getenv("GPRX_LML_GRAD") && std::string(std::getenv("GPRX_LML_GRAD")) == "direct";
         const int64_t np = M->np, npf = round_up(M->n, GT);
-        if (!direct_grad && npf == np && pairs_grad_supported<T>(K)) {
+        if (!env_lml_grad_direct() && npf == np && pairs_grad_supported<T>(K)) {
             // pair statistics (and the periodic b-derivative statistic) on the MFMA units
             const int64_t kg = pairs_grad_feature_cols<T>(K, M->d);
             train_features<T>(M, false, np);
@@ -420,6 +419,120 @@ gprx_status model_lml(gprx_model* M, uint32_t flags, double* value, double* grad
             const int np = leaf_type_nparams(t);
             for (int q = 0; q < np; q++) grad[K.param_base[l] + q] = 0.5 * acc[l * 3 + q];
         }
+    }
+    return GPRX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// Leave-one-out cross-validation (k_loo.hip; GPML 5.4.2, not in the reference): the held-out
+// means and variances of every sample, the predictive log probability and its gradient from
+// what a Cholesky fit leaves resident.  A fitted model is read, never refitted; the call's own
+// buffers: looVec (u, sqrt w, u / sqrt w, a), looPart (the reductions' partials), looOut (the
+// results), looH (H / 2), and V, which nothing reads once C = V V^T exists, for B.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+gprx_status model_loo(gprx_model* M, uint32_t flags, double* value, void* mean, void* var, double* grad,
+                      int32_t* nparams) {
+    gprx_ctx* ctx = M->ctx;
+    const bool want_grad = grad && (flags & GPRX_LOO_GRAD);
+    GPRX_REQUIRE(!((ctx->hc && ctx->world > 1) || ctx->virt), GPRX_ERR_STATE,
+                 "gprx_model_loo: sharded contexts (multi-rank or virtual-rank) are not supported");
+    GPRX_REQUIRE(!M->sparse_cov, GPRX_ERR_STATE, "gprx_model_loo: a sparse-covariance model holds no factor");
+    GPRX_REQUIRE(!(M->fitted && M->dist_fitted), GPRX_ERR_STATE, "gprx_model_loo: the model was fitted sharded");
+    GPRX_REQUIRE(!(M->fitted && M->method == 1), GPRX_ERR_STATE,
+                 "gprx_model_loo: the model's factor is an LU (leave-one-out needs the Cholesky factor)");
+    GPRX_REQUIRE(!(M->host_k && want_grad), GPRX_ERR_STATE,
+                 "gprx_model_loo: a caller-evaluated kernel has no device derivative (values only)");
+    GPRX_REQUIRE(!(want_grad && M->m != 1), GPRX_ERR_DIM,
+                 "gprx_model_loo: the gradient supports one output dimension only, as gprx_model_lml");
+    if (!M->fitted) {  // data, kernel and noise but no fit: fitted here, the inverse riding along for a gradient
+        M->want_inv = want_grad;
+        gprx_status st;
+        try {
+            st = model_fit<T>(M, GPRX_FIT_NO_LU_FALLBACK, nullptr);
+        } catch (...) {
+            M->want_inv = false;
+            throw;
+        }
+        M->want_inv = false;
+        if (st != GPRX_OK) return st;
+    }
+    hipStream_t s = ctx->stream;
+    const KCanon<T>& K = kcanon<T>(M);
+    const int64_t n = M->n, np = M->np;
+    const int m = M->m;
+    if (want_grad && !M->inv_ready) {
+        model_inverse<T>(M);
+        M->inverse_done();
+    }
+    const int64_t nvb = (np + 255) / 256;
+    M->looPart.ensure(sizeof(double) * (loo_part_elems(np) + nvb + 1));
+    M->looOut.ensure(sizeof(T) * (n * m + n));
+    double* part = M->looPart.as<double>();
+    double* vpart = part + loo_part_elems(np);
+    double* dval = vpart + nvb;
+    T* dmean = M->looOut.as<T>();
+    T* dvar = dmean + n * m;
+    T *u = nullptr, *sw = nullptr, *r = nullptr, *a = nullptr;
+    if (want_grad) {
+        M->looVec.ensure(sizeof(T) * 4 * np);
+        u = M->looVec.as<T>();
+        sw = u + np;
+        r = sw + np;
+        a = r + np;
+    }
+    const double* cpart = nullptr;
+    if (!M->inv_ready) {  // diag(C) without C: the squared row norms of V = L^{-T}
+        M->V.ensure(sizeof(T) * np * np);
+        launch_factor_inverse_t<T>(M->A.as<T>(), M->ld, np, M->Linv.as<T>(), M->V.as<T>(), s);
+        launch_loo_diag<T>(M->V.as<T>(), np, part, s);
+        cpart = part;
+    }
+    launch_loo_vectors<T>(M->alpha.as<T>(), M->Y.as<T>(), n, np, m, cpart, M->C.as<T>(), np, dmean, dvar, u, sw, r, vpart,
+                          dval, s);
+    double v = 0;
+    download(&v, dval, sizeof(double), s);
+    if (!std::isfinite(v))
+        throw Error{GPRX_ERR_NONFINITE, "gprx_model_loo: the leave-one-out log probability is not finite."};
+    if (value) *value = v;
+    if (nparams) *nparams = M->host_k ? 0 : K.nparams;
+    if (mean) download(mean, dmean, sizeof(T) * n * m, s);
+    if (var) download(var, dvar, sizeof(T) * n, s);
+    if (!want_grad) return GPRX_OK;
+
+    // B = sym(C) diag(sqrt w) into V, a = C u, H / 2 = B B^T / 2 (lower) on the tile mainloop
+    M->V.ensure(sizeof(T) * np * np);
+    M->looH.ensure(sizeof(T) * np * np);
+    launch_loo_weights<T>(M->C.as<T>(), np, np, sw, r, M->V.as<T>(), part, a, s);
+    GPRX_HIP(hipMemsetAsync(M->looH.p, 0, sizeof(T) * np * np, s));
+    launch_syrk_splitk<T>(M->looH.as<T>(), np, 0, M->V.as<T>(), np, np, np, np, 1, T(0.5), s);
+    // sum_kl dK_kl/dp ((a_k alpha_l + a_l alpha_k) / 2 - H_kl / 2): the LML's gradient pass in
+    // its two-vector mode
+    M->grad.ensure(sizeof(double) * MAX_LEAF * 3);
+    GPRX_HIP(hipMemsetAsync(M->grad.p, 0, sizeof(double) * MAX_LEAF * 3, s));
+    const int64_t npf = round_up(n, GT);
+    if (!env_lml_grad_direct() && npf == np && pairs_grad_supported<T>(K)) {
+        const int64_t kg = pairs_grad_feature_cols<T>(K, M->d);
+        train_features<T>(M, false, np);
+        train_features<T>(M, true, np);
+        const KCanon<T>* kdev = M->kfit.put(K, s);
+        M->scratch1.ensure(sizeof(T) * np * std::max<int64_t>(kg, 1));
+        M->scratch2.ensure(sizeof(T) * np * std::max<int64_t>(kg, 1));
+        const int64_t nt = np / GT;
+        M->pack.ensure(sizeof(double) * MAX_LEAF * 3 * nt * (nt + 1) / 2);
+        launch_loo_grad_mma<T>(K, kdev, M->X.as<T>(), n, M->d, M->featU.as<T>(), M->featV.as<T>(), M->scratch1.as<T>(),
+                               M->scratch2.as<T>(), np, a, M->alpha.as<T>(), M->looH.as<T>(), np, M->pack.as<double>(),
+                               M->grad.as<double>(), s);
+    } else {
+        ensure_train_tables<T>(M);
+        launch_lml_grad<T>(K, M->X.as<T>(), M->tab.as<T>(), n, M->d, a, M->looH.as<T>(), np, M->grad.as<double>(), s,
+                           M->alpha.as<T>());
+    }
+    double acc[MAX_LEAF * 3];
+    download(acc, M->grad.p, sizeof(acc), s);
+    for (int l = 0; l < K.nleaf; l++) {
+        const int npl = leaf_type_nparams(K.leaf[l].type);
+        for (int q = 0; q < npl; q++) grad[K.param_base[l] + q] = acc[l * 3 + q];
     }
     return GPRX_OK;
 }
@@ -514,6 +627,7 @@ gprx_status model_lml_dk(gprx_model* M, uint32_t flags, const void* dK, int32_t 
     template gprx_status model_posterior_cov<T>(gprx_model*, const void*, const void*, int64_t, void*);    \
     template gprx_status model_core_matrix<T>(gprx_model*, void*);                                         \
     template gprx_status model_lml<T>(gprx_model*, uint32_t, double*, double*, int32_t*, double*);         \
+    template gprx_status model_loo<T>(gprx_model*, uint32_t, double*, void*, void*, double*, int32_t*);    \
     template gprx_status model_predict_kx<T>(gprx_model*, const void*, const void*, int64_t, void*, void*); \
     template gprx_status model_posterior_cov_kx<T>(gprx_model*, const void*, const void*, const void*,     \
                                                    int64_t, void*);                                        \

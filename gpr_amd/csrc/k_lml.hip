@@ -91,11 +91,9 @@ void launch_sum_partials(T* S, int64_t stride, int P, hipStream_t s) {
     hipLaunchKernelGGL(sum_partials_kernel<T>, dim3((unsigned)((stride + 255) / 256)), dim3(256), 0, s, S, stride, P);
 }
 
+// V = L^{-T} (upper, np x np, ld np; the lower triangle zero) from the stored factor
 template <typename T>
-void launch_spd_inverse_from_factor(const T* A, int64_t ldA, int64_t np, const T* Linv, T* V, T* C, hipStream_t s) {
-    Prof* saved = g_prof;  // the trsm/gemm pieces are accounted as one INVERSE phase
-    ProfScope ps(KC_INVERSE, s, 2.0 * (double)np * np * np / 3.0, 0.0);
-    g_prof = nullptr;
+static void factor_inverse_t(const T* A, int64_t ldA, int64_t np, const T* Linv, T* V, hipStream_t s) {
     GPRX_HIP(hipMemsetAsync(V, 0, sizeof(T) * np * np, s));
     hipLaunchKernelGGL(set_diag_kernel<T>, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, V, np, (int64_t)0, np,
                        T(1));
@@ -110,6 +108,24 @@ void launch_spd_inverse_from_factor(const T* A, int64_t ldA, int64_t np, const T
             launch_gemm_nt<T>(V + rows * np, np, Vk, np, A + rows + k0 * ldA, ldA, rows, rem, DB, T(-1), T(1), false,
                               s);
     }
+}
+
+// (the leave-one-out values need V alone: diag(C) is its rows' squared norms, k_loo.hip)
+template <typename T>
+void launch_factor_inverse_t(const T* A, int64_t ldA, int64_t np, const T* Linv, T* V, hipStream_t s) {
+    Prof* saved = g_prof;
+    ProfScope ps(KC_INVERSE, s, (double)np * np * np / 3.0, 0.0);
+    g_prof = nullptr;
+    factor_inverse_t<T>(A, ldA, np, Linv, V, s);
+    g_prof = saved;
+}
+
+template <typename T>
+void launch_spd_inverse_from_factor(const T* A, int64_t ldA, int64_t np, const T* Linv, T* V, T* C, hipStream_t s) {
+    Prof* saved = g_prof;  // the trsm/gemm pieces are accounted as one INVERSE phase
+    ProfScope ps(KC_INVERSE, s, 2.0 * (double)np * np * np / 3.0, 0.0);
+    g_prof = nullptr;
+    factor_inverse_t<T>(A, ldA, np, Linv, V, s);
     // C = V V^T, lower; V[i][k] = 0 for k < i so tile row i0 starts its K loop at i0
     launch_gemm_nt_kskip<T>(C, np, V, np, V, np, np, np, np, s);
     g_prof = saved;
@@ -128,7 +144,9 @@ struct GradSmem {
 
 // CROSS: rows from X (n), columns from Xb (nb), every tile (ntr row tiles), weights
 // alpha_i beta_j - C_ij without doubling (the sparse likelihood, include/SparseLikelihood.h:317-340).
-template <typename T, int NPER, bool CROSS = false>
+// SYM2 (not CROSS): the lower triangle with doubling and the two-vector symmetric weights
+// (alpha_i beta_j + alpha_j beta_i) / 2 - C_ij (the leave-one-out gradient, k_loo.hip).
+template <typename T, int NPER, bool CROSS = false, bool SYM2 = false>
 __global__ __launch_bounds__(256) void lml_grad_kernel(KCanon<T> K, const T* __restrict__ X, const T* __restrict__ tab,
                                                        int64_t n, int d, const T* __restrict__ alpha,
                                                        const T* __restrict__ C, int64_t ldc, double* __restrict__ gout,
@@ -138,7 +156,7 @@ __global__ __launch_bounds__(256) void lml_grad_kernel(KCanon<T> K, const T* __r
     __shared__ __attribute__((aligned(16))) GradSmem<T, NPER> sm;
     const T* __restrict__ Xc = CROSS ? Xb : X;
     const T* __restrict__ tc = CROSS ? tabB : tab;
-    const T* __restrict__ bv = CROSS ? beta : alpha;
+    const T* __restrict__ bv = (CROSS || SYM2) ? beta : alpha;
     const int64_t ncol = CROSS ? nb : n;
     int64_t ti, tj;
     if (CROSS) {
@@ -232,7 +250,8 @@ __global__ __launch_bounds__(256) void lml_grad_kernel(KCanon<T> K, const T* __r
         for (int b = 0; b < 4; b++) {
             const int64_t gj = j0 + ty * 4 + b;
             if (gi >= n || gj >= ncol || (!CROSS && gi < gj)) continue;
-            const T w = (alpha[gi] * bv[gj] - C[gi + gj * ldc]) * ((CROSS || gi == gj) ? T(1) : T(2));
+            const T ab = SYM2 ? T(0.5) * fma(alpha[gi], bv[gj], alpha[gj] * bv[gi]) : alpha[gi] * bv[gj];
+            const T w = (ab - C[gi + gj * ldc]) * ((CROSS || gi == gj) ? T(1) : T(2));
             T lv[MAX_LEAF];
 #pragma unroll
             for (int l = 0; l < MAX_LEAF; l++)
@@ -307,13 +326,23 @@ struct GradSlots {
 
 template <typename T>
 void launch_lml_grad(const KCanon<T>& K, const T* X, const T* tab, int64_t n, int d, const T* alpha, const T* C,
-                     int64_t ldc, double* acc, hipStream_t s) {
+                     int64_t ldc, double* acc, hipStream_t s, const T* beta) {
     const int64_t nt = (n + BT - 1) / BT;
     const unsigned grid = (unsigned)(nt * (nt + 1) / 2);
     if (grid == 0) return;
     ProfScope ps(KC_LML_GRAD, s, 0.0, (double)sizeof(T) * ((double)n * (n + 1) / 2 + (double)n * d));
     GradSlots slots(grid, s);
-    if (K.nper == 0)
+    if (beta) {  // the two-vector symmetric weights
+        if (K.nper == 0)
+            hipLaunchKernelGGL((lml_grad_kernel<T, 0, false, true>), dim3(grid), dim3(256), 0, s, K, X, tab, n, d, alpha,
+                               C, ldc, slots.p, X, tab, n, beta, (int64_t)1);
+        else if (K.nper == 1)
+            hipLaunchKernelGGL((lml_grad_kernel<T, 1, false, true>), dim3(grid), dim3(256), 0, s, K, X, tab, n, d, alpha,
+                               C, ldc, slots.p, X, tab, n, beta, (int64_t)1);
+        else
+            hipLaunchKernelGGL((lml_grad_kernel<T, 2, false, true>), dim3(grid), dim3(256), 0, s, K, X, tab, n, d, alpha,
+                               C, ldc, slots.p, X, tab, n, beta, (int64_t)1);
+    } else if (K.nper == 0)
         hipLaunchKernelGGL((lml_grad_kernel<T, 0>), dim3(grid), dim3(256), 0, s, K, X, tab, n, d, alpha, C, ldc,
                            slots.p, X, tab, n, alpha, (int64_t)1);
     else if (K.nper == 1)
@@ -357,8 +386,9 @@ void launch_lml_grad_cross(const KCanon<T>& K, const T* Xa, const T* tabA, int64
     template void launch_sym_fill<T>(T*, int64_t, int64_t, hipStream_t);                                       \
     template void launch_sum_partials<T>(T*, int64_t, int, hipStream_t);                                        \
     template void launch_spd_inverse_from_factor<T>(const T*, int64_t, int64_t, const T*, T*, T*, hipStream_t); \
+    template void launch_factor_inverse_t<T>(const T*, int64_t, int64_t, const T*, T*, hipStream_t);           \
     template void launch_lml_grad<T>(const KCanon<T>&, const T*, const T*, int64_t, int, const T*, const T*,   \
-                                     int64_t, double*, hipStream_t);
+                                     int64_t, double*, hipStream_t, const T*);
 GPRX_INST(double)
 GPRX_INST(float)
 #undef GPRX_INST

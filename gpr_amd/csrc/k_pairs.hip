@@ -372,7 +372,10 @@ __global__ void grad_features_kernel(const T* __restrict__ X, int64_t n, int d, 
 // CROSS: every tile of a rectangular pair block (rows: the U features, nf rows, nrow live;
 // columns: the V features, nfv rows, ncol live) with weights w_ij = alpha_i beta_j - C_ij and
 // no diagonal (the sparse likelihood's sum over K(X, Xm), include/SparseLikelihood.h:317-340).
-template <typename T, int NPER, bool R2, bool CROSS, bool MAT>
+// SYM2 (not CROSS): the two-vector symmetric weights w_ij = (alpha_i beta_j + alpha_j beta_i) / 2
+// - C_ij of the leave-one-out gradient (k_loo.hip), whose rank-2 term a alpha^T is not symmetric
+// while the sum runs over the lower triangle with doubling.
+template <typename T, int NPER, bool R2, bool CROSS, bool MAT, bool SYM2 = false>
 __device__ __forceinline__ void grad_mma_body(const KCanon<T>* __restrict__ Kd, const T* __restrict__ FU,
                                               const T* __restrict__ FV, const T* __restrict__ GU,
                                               const T* __restrict__ GV, int64_t nf, int Kr, int Kp, int Kf, T hd,
@@ -440,7 +443,8 @@ __device__ __forceinline__ void grad_mma_body(const KCanon<T>* __restrict__ Kd, 
                 const bool in = gi < n && gj < ncol_ && (CROSS || gi >= gj);
                 const int64_t ci = in ? gi : 0, cj = in ? gj : 0;
                 const T cv = ct ? -ct[in ? (gi - i0) + (gj - j0) * DB : 0] : C[ci + cj * ldc];
-                const T v = alpha[ci] * bvec[cj] - cv;
+                const T v = SYM2 ? T(0.5) * fma(alpha[ci], beta[cj], alpha[cj] * beta[ci]) - cv
+                                 : alpha[ci] * bvec[cj] - cv;
                 wt[x][y][reg] = in ? (CROSS ? v : v * (gi == gj ? T(1) : T(2))) : T(0);
             }
         });
@@ -603,6 +607,17 @@ __global__ __launch_bounds__(NT) void grad_mma_kernel_m(GPRX_GRAD_ARGS) {
     grad_mma_body<T, NPER, R2, CROSS, true>(Kd, FU, FV, GU, GV, nf, Kr, Kp, Kf, hd, alpha, C, ldc, n, part, ctab, nfv,
                                             ncol, beta);
 }
+// the two-vector symmetric forms (SYM2): alpha and beta both n long
+template <typename T, int NPER, bool R2>
+__global__ __launch_bounds__(NT) void grad_mma_kernel2(GPRX_GRAD_ARGS) {
+    grad_mma_body<T, NPER, R2, false, false, true>(Kd, FU, FV, GU, GV, nf, Kr, Kp, Kf, hd, alpha, C, ldc, n, part, ctab,
+                                                   nfv, ncol, beta);
+}
+template <typename T, int NPER, bool R2>
+__global__ __launch_bounds__(NT) void grad_mma_kernel2_m(GPRX_GRAD_ARGS) {
+    grad_mma_body<T, NPER, R2, false, true, true>(Kd, FU, FV, GU, GV, nf, Kr, Kp, Kf, hd, alpha, C, ldc, n, part, ctab,
+                                                  nfv, ncol, beta);
+}
 #undef GPRX_GRAD_ARGS
 
 // gout[p] = sum over tiles of part[tile][p], in tile order
@@ -736,12 +751,13 @@ int64_t pairs_grad_feature_cols(const KCanon<T>& K, int d) {
     return K.nper ? pr::rup(4 * d, pr::KG) : 0;
 }
 
-// acc[3 l + q] = sum_{i >= j} w_ij d leaf_l / d p_q, from the features of launch_pair_features
-// (FU, FV: nf rows) and grad features GU, GV (computed here); part: ntiles * 3 MAX_LEAF doubles
-template <typename T>
-void launch_lml_grad_mma(const KCanon<T>& K, const KCanon<T>* Kd, const T* X, int64_t n, int d, const T* FU,
-                         const T* FV, T* GU, T* GV, int64_t nf, const T* alpha, const T* C, int64_t ldc, double* part,
-                         double* acc, hipStream_t s, const uint64_t* ctab) {
+// The symmetric pass shared by launch_lml_grad_mma and launch_loo_grad_mma: grad features, one
+// workgroup per lower tile through `dispatch(go)` (which picks the kernel for the tree and hands
+// it to go), the tiles' partials reduced in a fixed order.
+template <typename T, typename Dispatch>
+static void grad_mma_pass(const KCanon<T>& K, const KCanon<T>* Kd, const T* X, int64_t n, int d, const T* FU,
+                          const T* FV, T* GU, T* GV, int64_t nf, const T* alpha, const T* beta, const T* C, int64_t ldc,
+                          double* part, double* acc, hipStream_t s, const uint64_t* ctab, Dispatch&& dispatch) {
     const int Kr = pr::kr_of(K, d), Kp = pr::kp_of(K, d), Kf = (int)pairs_grad_feature_cols(K, d);
     if (K.nper) {
         const dim3 g((unsigned)((nf + 255) / 256));
@@ -756,14 +772,25 @@ void launch_lml_grad_mma(const KCanon<T>& K, const KCanon<T>* Kd, const T* X, in
     auto go = [&](auto kfn) {
         GPRX_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kfn, grid, dim3(mm::NT), lds, s, Kd, FU, FV, (const T*)GU, (const T*)GV, nf, Kr, Kp, Kf,
-                           T(0.5) * T(d), alpha, C, ldc, n, part, ctab, nf, n, alpha);
+                           T(0.5) * T(d), alpha, C, ldc, n, part, ctab, nf, n, beta);
     };
-    const bool mat = has_matern(K);
-    if (K.nper && K.need_r2) mat ? go(pr::grad_mma_kernel_m<T, 1, true>) : go(pr::grad_mma_kernel<T, 1, true>);
-    else if (K.nper) go(pr::grad_mma_kernel<T, 1, false>);
-    else mat ? go(pr::grad_mma_kernel_m<T, 0, true>) : go(pr::grad_mma_kernel<T, 0, true>);
+    dispatch(go);
     hipLaunchKernelGGL(pr::grad_reduce_kernel, dim3(MAX_LEAF * 3), dim3(256), 0, s, (const double*)part, ntiles, acc);
     GPRX_HIP(hipGetLastError());
+}
+
+// acc[3 l + q] = sum_{i >= j} w_ij d leaf_l / d p_q, from the features of launch_pair_features
+// (FU, FV: nf rows) and grad features GU, GV (computed here); part: ntiles * 3 MAX_LEAF doubles
+template <typename T>
+void launch_lml_grad_mma(const KCanon<T>& K, const KCanon<T>* Kd, const T* X, int64_t n, int d, const T* FU,
+                         const T* FV, T* GU, T* GV, int64_t nf, const T* alpha, const T* C, int64_t ldc, double* part,
+                         double* acc, hipStream_t s, const uint64_t* ctab) {
+    grad_mma_pass<T>(K, Kd, X, n, d, FU, FV, GU, GV, nf, alpha, alpha, C, ldc, part, acc, s, ctab, [&](auto& go) {
+        const bool mat = has_matern(K);
+        if (K.nper && K.need_r2) mat ? go(pr::grad_mma_kernel_m<T, 1, true>) : go(pr::grad_mma_kernel<T, 1, true>);
+        else if (K.nper) go(pr::grad_mma_kernel<T, 1, false>);
+        else mat ? go(pr::grad_mma_kernel_m<T, 0, true>) : go(pr::grad_mma_kernel<T, 0, true>);
+    });
 }
 
 // Cross form: acc[3 l + q] = sum_{i < na, j < nb} (a_i b_j - C_ij) d leaf_l(xa_i, xb_j) / d p_q
@@ -829,6 +856,23 @@ TileBuild<T> pairs_tile_build(const KCanon<T>& K, const KCanon<T>* Kd, const T* 
     return b;
 }
 
+// The same pass with the two-vector symmetric weights (alpha_i beta_j + alpha_j beta_i) / 2 - C_ij:
+// the leave-one-out gradient (k_loo.hip), whose rank-2 term is not symmetric.  (Defined and
+// instantiated last: its kernels come after every other one of this file in the code object.)
+template <typename T>
+void launch_loo_grad_mma(const KCanon<T>& K, const KCanon<T>* Kd, const T* X, int64_t n, int d, const T* FU,
+                         const T* FV, T* GU, T* GV, int64_t nf, const T* alpha, const T* beta, const T* C, int64_t ldc,
+                         double* part, double* acc, hipStream_t s) {
+    grad_mma_pass<T>(K, Kd, X, n, d, FU, FV, GU, GV, nf, alpha, beta, C, ldc, part, acc, s, (const uint64_t*)nullptr,
+                     [&](auto& go) {
+                         const bool mat = has_matern(K);
+                         if (K.nper && K.need_r2)
+                             mat ? go(pr::grad_mma_kernel2_m<T, 1, true>) : go(pr::grad_mma_kernel2<T, 1, true>);
+                         else if (K.nper) go(pr::grad_mma_kernel2<T, 1, false>);
+                         else mat ? go(pr::grad_mma_kernel2_m<T, 0, true>) : go(pr::grad_mma_kernel2<T, 0, true>);
+                     });
+}
+
 #define GPRX_PAIRS_INST(T)                                                                                    \
     template bool pairs_grad_supported<T>(const KCanon<T>&);                                                  \
     template int64_t pairs_grad_feature_cols<T>(const KCanon<T>&, int);                                       \
@@ -855,5 +899,11 @@ TileBuild<T> pairs_tile_build(const KCanon<T>& K, const KCanon<T>* Kd, const T* 
 GPRX_PAIRS_INST(double)
 GPRX_PAIRS_INST(float)
 #undef GPRX_PAIRS_INST
+template void launch_loo_grad_mma<double>(const KCanon<double>&, const KCanon<double>*, const double*, int64_t, int,
+                                          const double*, const double*, double*, double*, int64_t, const double*,
+                                          const double*, const double*, int64_t, double*, double*, hipStream_t);
+template void launch_loo_grad_mma<float>(const KCanon<float>&, const KCanon<float>*, const float*, int64_t, int,
+                                         const float*, const float*, float*, float*, int64_t, const float*,
+                                         const float*, const float*, int64_t, double*, double*, hipStream_t);
 
 }  // namespace gprx

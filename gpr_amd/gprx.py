@@ -31,6 +31,7 @@ LML_GRAD = 1
 LML_COMPAT = 2
 LML_DISTRIBUTED = 4
 LML_FORCE_LU = 8
+LOO_GRAD = 1
 
 STATUS = {0: "OK", 1: "NONFINITE", 2: "NOT_SPD", 3: "SINGULAR", 4: "DIM", 5: "HIP", 6: "RCCL", 7: "OOM",
           8: "ARG", 9: "STATE", 10: "NO_DEVICE"}
@@ -48,7 +49,7 @@ EXPORTED = [
     "gprx_model_set_kernel_matrix", "gprx_model_predict_kx", "gprx_model_posterior_cov_kx", "gprx_model_lml_dk",
     "gprx_model_set_sparse_cov", "gprx_sparse_lml",
     "gprx_device_alloc", "gprx_device_free", "gprx_device_upload", "gprx_device_download",
-    "gprx_model_append", "gprx_model_remove",
+    "gprx_model_append", "gprx_model_remove", "gprx_model_loo",
 ]
 
 
@@ -147,6 +148,9 @@ def lib():
         L.gprx_model_core_matrix.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_lml.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                      ctypes.c_void_p, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_double)]
+        L.gprx_model_loo.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
+                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                     ctypes.POINTER(ctypes.c_int32)]
         L.gprx_model_set_kernel_matrix.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_set_sparse_cov.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_predict_kx.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
@@ -799,3 +803,20 @@ class Model:
         ld = ctypes.c_double()
         self._c(lib().gprx_model_lml(self.h, flags, ctypes.byref(v), _ptr(g), ctypes.byref(npar), ctypes.byref(ld)))
         return v.value, (g[:npar.value].copy() if grad else None), ld.value
+
+    def loo(self, grad=False):
+        """Leave-one-out cross-validation (gprx_model_loo; GPML 5.4.2) -> (value, mean, var, grad):
+        the predictive log probability summed over the label columns, every sample's held-out mean
+        (n x m) and variance (n), and with grad=True (m = 1, a device kernel) the value's gradient
+        in the kernel parameters, else None.  A model fitted by Cholesky is read as it is (after
+        append / remove too); an unfitted one is fitted first."""
+        if grad and self._host_kernel():
+            raise GprxError(9, "loo: a caller-evaluated kernel has no device derivative (grad=False works)")
+        v = ctypes.c_double()
+        mean = np.empty((self.n, self.m), self.dtype)
+        var = np.empty(self.n, self.dtype)
+        g = np.zeros(MAX_KPARAMS, np.float64)
+        npar = ctypes.c_int32()
+        self._c(lib().gprx_model_loo(self.h, LOO_GRAD if grad else 0, ctypes.byref(v), _ptr(mean), _ptr(var),
+                                     _ptr(g) if grad else None, ctypes.byref(npar)))
+        return v.value, mean, var, (g[:npar.value].copy() if grad else None)

@@ -303,6 +303,19 @@ const typename GaussianProcess<T>::MatrixType& GaussianProcess<T>::GetCoreMatrix
     return m_CoreMatrix;
 }
 
+template <class T>
+T GaussianProcess<T>::LeaveOneOut(MatrixType& mean, VectorType& variance) {
+    Initialize();
+    std::lock_guard<std::mutex> lk(m_DevMu);
+    EnsureFactor();
+    const std::size_t n = m_SampleVectors.size();
+    mean.resize(n, m_OutputDimension);
+    variance = VectorType(n);
+    double value = 0;
+    ThrowIfFailed(gprx_model_loo(m_Model, 0u, &value, mean.data(), variance.data(), nullptr, nullptr), DefaultContext());
+    return (T)value;
+}
+
 // lib/GaussianProcess.cpp:54-61
 template <class T>
 typename GaussianProcess<T>::VectorType GaussianProcess<T>::Predict(const VectorType& x) {

@@ -125,6 +125,11 @@ public:
     // The explicit core matrix (K + sigma^2 I)^{-1}, materialised from the device factor.
     const MatrixType& GetCoreMatrix();
 
+    // Leave-one-out cross-validation (gprx_model_loo; not in the reference): every sample's mean
+    // (n x m) and variance (n) predicted from all the others, from the device's Cholesky factor
+    // without refitting.  Returns the predictive log probability summed over the outputs.
+    TScalarType LeaveOneOut(MatrixType& mean, VectorType& variance);
+
 protected:
     KernelTypePointer m_Kernel;
     TScalarType m_Sigma;

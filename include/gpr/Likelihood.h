@@ -1,4 +1,4 @@
-// gpr/Likelihood.h — GaussianLikelihood / GaussianLogLikelihood over libgprx.
+// gpr/Likelihood.h — GaussianLikelihood / GaussianLogLikelihood / LeaveOneOutLogLikelihood over libgprx.
 //
 // Same classes and entry points as the reference (include/Likelihood.h:34-354):
 // operator()(gp), GetParameterDerivatives(gp), GetValueAndParameterDerivatives(gp),
@@ -88,6 +88,29 @@ protected:
         e.grad.resize(np);
         return e;
     }
+    // The leave-one-out predictive log probability (gprx_model_loo) on the gp's current
+    // samples/kernel/noise, fitted by that call; the same bookkeeping as Evaluate.
+    Eval EvaluateLeaveOneOut(const GaussianProcessTypePointer gp, bool grad) const {
+        std::lock_guard<std::mutex> lk(gp->m_DevMu);
+        gp->UploadState();
+        if (grad && gp->m_OutputDimension != 1)
+            throw std::string("LeaveOneOutLogLikelihood: the gradient supports one output dimension");
+        if (grad && gp->m_HostKernel)
+            throw std::string("LeaveOneOutLogLikelihood: a kernel with no device form has no device gradient");
+        Eval e;
+        int32_t np = 0;
+        e.grad.resize(GPRX_MAX_KNODES * 3);
+        ThrowIfFailed(gprx_model_loo(gp->m_Model, grad ? GPRX_LOO_GRAD : 0u, &e.value, nullptr, nullptr,
+                                     grad ? e.grad.data() : nullptr, &np),
+                      DefaultContext());
+        gp->m_DeviceFactor = true;
+        gp->m_FitCholesky = false;  // (as Evaluate: not a factor Update() may extend)
+        gp->m_CoreValid = false;
+        if (gp->m_Initialized && gp->m_RegressionVectors.rows() == gp->m_SampleVectors.size())
+            ThrowIfFailed(gprx_model_set_alpha(gp->m_Model, gp->m_RegressionVectors.data()), DefaultContext());
+        e.grad.resize(grad ? np : 0);
+        return e;
+    }
 };
 
 // include/Likelihood.h:94-150: exp(data fit) / sqrt(det) / (2 pi)^{N/2}
@@ -159,6 +182,44 @@ private:
     static VectorType Value(const typename Superclass::Eval& e) {
         if (std::isinf(e.value))
             throw std::string("GaussianLogLikelihood::GetValueAndParameterDerivatives: likelihood is infinite.");
+        VectorType v(1);
+        v[0] = (TScalarType)e.value;
+        return v;
+    }
+    static VectorType Grad(const typename Superclass::Eval& e) {
+        VectorType g(e.grad.size());
+        for (std::size_t p = 0; p < e.grad.size(); p++) g[p] = (TScalarType)e.grad[p];
+        return g;
+    }
+};
+
+// The leave-one-out predictive log probability (Rasmussen & Williams, GPML 5.4.2; not in the
+// reference) as a Likelihood: GaussianProcessInference::Optimize maximises it as it does the
+// marginal likelihood.  One device call (gprx_model_loo) fits the factor and evaluates value and
+// gradient; the value is summed over the output dimensions, the gradient needs one.
+template <class TScalarType>
+class LeaveOneOutLogLikelihood : public Likelihood<TScalarType> {
+public:
+    typedef Likelihood<TScalarType> Superclass;
+    typedef typename Superclass::VectorType VectorType;
+    typedef typename Superclass::GaussianProcessTypePointer GaussianProcessTypePointer;
+    typedef typename Superclass::ValueDerivativePair ValueDerivativePair;
+
+    LeaveOneOutLogLikelihood() {}
+    virtual VectorType operator()(const GaussianProcessTypePointer gp) const {
+        return Value(this->EvaluateLeaveOneOut(gp, false));
+    }
+    virtual VectorType GetParameterDerivatives(const GaussianProcessTypePointer gp) const {
+        return Grad(this->EvaluateLeaveOneOut(gp, true));
+    }
+    virtual ValueDerivativePair GetValueAndParameterDerivatives(const GaussianProcessTypePointer gp) const {
+        auto e = this->EvaluateLeaveOneOut(gp, true);
+        return std::make_pair(Value(e), Grad(e));
+    }
+    virtual std::string ToString() const { return "LeaveOneOutLogLikelihood"; }
+
+private:
+    static VectorType Value(const typename Superclass::Eval& e) {
         VectorType v(1);
         v[0] = (TScalarType)e.value;
         return v;

@@ -315,6 +315,25 @@ gprx_status gprx_model_core_matrix(gprx_model* model, void* C);
 gprx_status gprx_model_lml(gprx_model* model, uint32_t flags, double* value, double* grad, int32_t* nparams,
                            double* logdet);
 
+#define GPRX_LOO_GRAD 1u /* also compute the hyper-parameter gradient */
+/* Leave-one-out cross-validation (Rasmussen & Williams, GPML 5.4.2; not in the reference).  With
+ * C = (K + sigma^2 I)^{-1}, c = diag(C), alpha = C y, per label column:
+ *   mean_i = y_i - alpha_i / c_i,  var_i = 1 / c_i,
+ *   value  = sum_i -1/2 log var_i - (y_i - mean_i)^2 / (2 var_i) - 1/2 log 2pi   (summed over the columns)
+ * grad_p (m = 1) = sum_kl dK_kl/dp (a_k alpha_l - H_kl / 2), a = C (alpha / c),
+ * H = C diag((1 + alpha^2 / c) / c) C: one N^3 product whatever the number of parameters.
+ * mean is N x m and var is N, in the model's dtype; value, mean, var and grad may each be NULL;
+ * nparams receives the kernel's parameter count.
+ * A model FITTED BY CHOLESKY is used as it is, never refitted: after gprx_model_append or
+ * gprx_model_remove, after a refined fp32 fit, with an installed alpha.  The call then changes
+ * nothing a later call can observe (with GPRX_LOO_GRAD it leaves C formed).  A model with data,
+ * kernel and noise but no fit is fitted first, with GPRX_FIT_NO_LU_FALLBACK (GPRX_ERR_NOT_SPD).
+ * GPRX_ERR_STATE, model untouched: an LU factor, a sharded fit or a multi-rank / virtual-rank
+ * context, a sparse-covariance model, GPRX_LOO_GRAD with a caller-evaluated kernel (its values
+ * work).  GPRX_ERR_DIM: GPRX_LOO_GRAD with m != 1.  GPRX_ERR_NONFINITE: a non-finite value. */
+gprx_status gprx_model_loo(gprx_model* model, uint32_t flags, double* value, void* mean, void* var, double* grad,
+                           int32_t* nparams);
+
 /* SparseGaussianProcess::operator()(x,y) = k(x,y) - Kx^T Kmm^{-1} Ky + Kx^T RM Ky
  * (include/SparseGaussianProcess.h:94-106) on a model whose data are the inducing points:
  * W = Kmm^{-1} - RM (M x M, row-major, from gprx_sparse_fit) becomes resident, and
