@@ -311,6 +311,33 @@ gprx_status gprx_model_loo(gprx_model* M, uint32_t flags, double* value, void* m
     });
 }
 
+gprx_status gprx_model_posterior(gprx_model* M, const void* Xq, int64_t q, uint32_t flags, void* mean, void* cov) {
+    return model_call(
+        M, q >= 0, "gprx_model_posterior: NULL model or negative q", CALL_PROF | CALL_DEVICE,
+        [&] {
+            if (q == 0) return true;
+            GPRX_REQUIRE(Xq, GPRX_ERR_ARG, "gprx_model_posterior: NULL argument");
+            return false;
+        },
+        [&] { return by_dtype(M->dt, [&](auto t) { return model_posterior<decltype(t)>(M, Xq, q, flags, mean, cov); }); });
+}
+
+gprx_status gprx_model_sample(gprx_model* M, const void* Xq, int64_t q, int64_t nsamp, uint64_t seed, uint32_t flags,
+                              const void* z, double* jitter, void* out) {
+    return model_call(
+        M, q >= 0 && nsamp >= 0, "gprx_model_sample: NULL model or a negative count", CALL_PROF | CALL_DEVICE,
+        [&] {
+            if (q == 0 || nsamp == 0) return true;
+            GPRX_REQUIRE(Xq && out, GPRX_ERR_ARG, "gprx_model_sample: NULL argument");
+            return false;
+        },
+        [&] {
+            return by_dtype(M->dt, [&](auto t) {
+                return model_sample<decltype(t)>(M, Xq, q, nsamp, seed, flags, z, jitter, out);
+            });
+        });
+}
+
 gprx_status gprx_model_set_sparse_cov(gprx_model* M, const void* W) {
     return model_call(M, W, "gprx_model_set_sparse_cov: NULL argument", 0, [&] {
         GPRX_REQUIRE(M->has_data && M->has_kernel && !M->host_k, GPRX_ERR_STATE,
@@ -555,6 +582,28 @@ gprx_status gprx_dev_factor_update(gprx_ctx* ctx, gprx_dtype dtype, const void* 
 }
 
 int32_t gprx_dev_factor_update_width(void) { return factor_update_width(); }
+
+gprx_status gprx_dev_normals(gprx_ctx* ctx, gprx_dtype dtype, uint64_t seed, int64_t count, void* out_host) {
+    API_BEGIN
+    GPRX_REQUIRE(ctx && count >= 0 && (count == 0 || out_host), GPRX_ERR_ARG, "gprx_dev_normals: bad argument");
+    GPRX_REQUIRE(dtype == GPRX_F32 || dtype == GPRX_F64, GPRX_ERR_ARG, "gprx_dev_normals: bad dtype");
+    if (count == 0) return GPRX_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    GPRX_HIP(hipSetDevice(ctx->device));
+    DevBuf z;
+    z.ensure(esize(dtype) * count);
+    by_dtype(dtype, [&](auto t) { launch_normals<decltype(t)>(seed, count, z.as<decltype(t)>(), ctx->stream); });
+    download(out_host, z.p, esize(dtype) * count, ctx->stream);
+    return GPRX_OK;
+    API_END(ctx)
+}
+
+gprx_status gprx_dev_sample_phases(gprx_model* M, double* ms) {
+    return model_call(M, ms, "gprx_dev_sample_phases: NULL argument", 0, [&] {
+        std::memcpy(ms, M->psMs, sizeof(M->psMs));
+        return GPRX_OK;
+    });
+}
 
 gprx_status gprx_dev_build_matrix(gprx_ctx* ctx, gprx_dtype dt, const gprx_kernel_desc* k, const void* X, int64_t n,
                                   int32_t d, double sigma, int32_t path, void* K) {

@@ -794,6 +794,23 @@ void launch_loo_vectors(const T* alpha, const T* Y, int64_t n, int64_t np, int m
 template <typename T>
 void launch_loo_weights(const T* C, int64_t ldc, int64_t np, const T* sw, const T* r, T* B, double* part, T* a,
                         hipStream_t s);
+// ---- posterior sampling (k_sample.hip) --------------------------------------------------
+// out[e] = the normal number e of the stream `seed` (Philox4x32-10 + Box-Muller, computed in fp64,
+// rounded once to T), e < count; a value depends on (seed, e) alone
+template <typename T>
+void launch_normals(uint64_t seed, int64_t count, T* out, hipStream_t s);
+// z (ncols x q, row-major) into the product's operand Zp[col + r ldz] (ldz x qp, both multiples of
+// 128), zeros in the padding
+template <typename T>
+void launch_stage_normals(const T* z, int64_t ncols, int64_t q, T* Zp, int64_t ldz, int64_t qp, hipStream_t s);
+// the strict upper part of the n x n block L (ld) to zero
+template <typename T>
+void launch_zero_upper(T* L, int64_t ld, int64_t n, hipStream_t s);
+// out[i, p, c] (nsamp x q x m, row-major) = mean[p, c] (q x m) + C[p + (i m + c) ldc]
+template <typename T>
+void launch_sample_out(const T* C, int64_t ldc, const T* mean, int64_t nsamp, int64_t q, int m, T* out,
+                       hipStream_t s);
+
 template <typename T>
 void launch_set_identity_pad(T* A, int64_t ld, int64_t n, int64_t np, hipStream_t s);
 template <typename T>

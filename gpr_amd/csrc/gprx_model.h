@@ -212,6 +212,12 @@ struct gprx_model {
     // partials, the results on their way to the host and H / 2 (np x np; the call also writes B
     // into V, which nothing reads once C exists)
     gprx::DevBuf looVec, looPart, looOut, looH;
+    // gprx_model_posterior / gprx_model_sample workspace (the cross rows R are pvRa): the joint
+    // covariance (qp x qp, lower, unfactored), its factored copy with the diagonal blocks'
+    // inverses, the mean and the prior diagonal (q m + q), the normals (e-linear, then as the
+    // product's operand) and the product with the samples behind it
+    gprx::DevBuf psS, psL, psLinv, psVec, psZ, psZp, psOut;
+    double psMs[6] = {0, 0, 0, 0, 0, 0};  // the last sample call's device ms per phase (stats on)
     // a fit (a refit, an append, or the fit inside an LML call) and new data free the posterior
     // workspace when it is large (one big variance call must not leave too little HBM
     // for the next fit on the device); the LML's own gradient pass does not
@@ -222,6 +228,8 @@ struct gprx_model {
             pvFq.release();
         }
         if (looH.bytes > (size_t(1) << 30)) looH.release();
+        if (psS.bytes + psL.bytes + psLinv.bytes + psVec.bytes + psZ.bytes + psZp.bytes + psOut.bytes > (size_t(1) << 30))
+            for (gprx::DevBuf* b : {&psS, &psL, &psLinv, &psVec, &psZ, &psZp, &psOut}) b->release();
     }
     // the kernel trees on the device (uploaded when they change): the model's T tree, and an fp32
     // model's double tree (the refinement's)
@@ -283,6 +291,7 @@ struct gprx_model {
     //                                                             sharded fit
     //   loo               fitted by Cholesky: nothing; else as   fitted: inverse_done() once a gradient
     //                     its fit (no LU fallback)                  formed C; else as its fit
+    //   posterior, sample  nothing (the model is read)            -
     //   (first dense use of a sharded fit: dense_gathered())
     //
     // "fit" = fitted, has_alpha, inv_ready.  set_data, set_kernel, set_kernel_matrix and set_noise
@@ -520,6 +529,11 @@ gprx_status model_lml(gprx_model* M, uint32_t flags, double* value, double* grad
 template <typename T>
 gprx_status model_loo(gprx_model* M, uint32_t flags, double* value, void* mean, void* var, double* grad,
                       int32_t* nparams);
+template <typename T>
+gprx_status model_posterior(gprx_model* M, const void* Xq, int64_t q, uint32_t flags, void* mean, void* cov);
+template <typename T>
+gprx_status model_sample(gprx_model* M, const void* Xq, int64_t q, int64_t nsamp, uint64_t seed, uint32_t flags,
+                         const void* z, double* jitter, void* out);
 template <typename T>
 gprx_status model_predict_kx(gprx_model* M, const void* Kx, const void* Xq, int64_t q, void* mean, void* deriv);
 template <typename T>

@@ -1,42 +1,78 @@
 // gprx_query.cpp — what reads a fitted model: predict, the posterior covariance (dense, LU, sharded,
-// sparse), the core matrix, the log marginal likelihood, the leave-one-out cross-validation and the
-// caller-evaluated-kernel forms.
+// sparse), the core matrix, the log marginal likelihood, the leave-one-out cross-validation, the
+// joint posterior with its draws and the caller-evaluated-kernel forms.
 #include "gprx_model.h"
 
 namespace gprx {
 
+// the mean (q x m, row-major) of the staged queries Q into dmean, and with dder their derivative
+// (q x d x m): what gprx_model_predict, _posterior and _sample all return as the mean
 template <typename T>
-gprx_status model_predict(gprx_model* M, const void* Xq, int64_t q, void* mean, void* deriv) {
-    GPRX_REQUIRE(M->has_alpha, GPRX_ERR_STATE, "GaussianProcess::ComputeKernelVectorInternal: gaussian process is not initialized.");
-    GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE, "gprx: a caller-evaluated kernel predicts through gprx_model_predict_kx");
+static void predict_staged(gprx_model* M, const Points<T>& Q, int64_t q, T* dmean, T* dder) {
     hipStream_t s = M->ctx->stream;
     const KCanon<T>& K = kcanon<T>(M);
     const int d = M->d, m = M->m;
-    Points<T> Q;
-    DevBuf dmean, dder;
-    stage_points<T>(Q, K, Xq, q, d, M->ctx->device, s, false);
-    dmean.ensure(sizeof(T) * q * m);
-    if (!deriv && !env_predict_direct() && pairs_mma_supported<T>(K, m)) {
+    if (!dder && !env_predict_direct() && pairs_mma_supported<T>(K, m)) {
         // mean only: MFMA pair statistics, K(Xq, X) never materialised (k_pairs.hip)
         const int64_t qp = round_up(q, GT), npf = round_up(M->n, GT);
         DevBuf fq;
         train_features<T>(M, true, npf);
         query_features<T>(M, Q.x, q, qp, fq);
         launch_predict_mma<T>(K, M->kfit.put(K, s), fq.as<T>(), qp, M->featV.as<T>(), npf, d, M->alpha.as<T>(), M->n, m,
-                              q, dmean.as<T>(), s);
-        download(mean, dmean.p, sizeof(T) * q * m, s);
-        return GPRX_OK;
+                              q, dmean, s);
+        GPRX_HIP(hipStreamSynchronize(s));  // (fq is freed on return)
+        return;
     }
-    if (deriv) dder.ensure(sizeof(T) * q * d * m);
-    const int64_t ncz = (int64_t)m * (deriv ? (1 + d) : 1);
+    const int64_t ncz = (int64_t)m * (dder ? (1 + d) : 1);
     M->scratch1.ensure(sizeof(T) * M->n * ncz);
     M->scratch2.ensure(sizeof(T) * q * ncz);
-    launch_predict<T>(K, M->X.as<T>(), M->tab.as<T>(), M->n, d, m, M->alpha.as<T>(), Q.x, Q.tab, q,
-                      dmean.as<T>(), deriv ? dder.as<T>() : nullptr, M->scratch1.as<T>(), M->scratch2.as<T>(), s);
+    launch_predict<T>(K, M->X.as<T>(), M->tab.as<T>(), M->n, d, m, M->alpha.as<T>(), Q.x, Q.tab, q, dmean, dder,
+                      M->scratch1.as<T>(), M->scratch2.as<T>(), s);
+}
+
+template <typename T>
+gprx_status model_predict(gprx_model* M, const void* Xq, int64_t q, void* mean, void* deriv) {
+    GPRX_REQUIRE(M->has_alpha, GPRX_ERR_STATE, "GaussianProcess::ComputeKernelVectorInternal: gaussian process is not initialized.");
+    GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE, "gprx: a caller-evaluated kernel predicts through gprx_model_predict_kx");
+    hipStream_t s = M->ctx->stream;
+    const int d = M->d, m = M->m;
+    Points<T> Q;
+    DevBuf dmean, dder;
+    stage_points<T>(Q, kcanon<T>(M), Xq, q, d, M->ctx->device, s, false);
+    dmean.ensure(sizeof(T) * q * m);
+    if (deriv) dder.ensure(sizeof(T) * q * d * m);
+    predict_staged<T>(M, Q, q, dmean.as<T>(), deriv ? dder.as<T>() : nullptr);
     download(mean, dmean.p, sizeof(T) * q * m, s);
     if (deriv) download(deriv, dder.p, sizeof(T) * q * d * m, s);
     return GPRX_OK;
 }
+
+// events around the phases of a call, recorded only with the context's statistics on
+struct PhaseClock {
+    hipStream_t s;
+    bool on;
+    std::vector<hipEvent_t> ev;
+    PhaseClock(gprx_ctx* ctx) : s(ctx->stream), on(ctx->prof.on) { mark(); }
+    void mark() {
+        if (!on) return;
+        hipEvent_t e;
+        GPRX_HIP(hipEventCreate(&e));
+        ev.push_back(e);
+        GPRX_HIP(hipEventRecord(e, s));
+    }
+    void read(double* ms, int n) {  // ms[k] = phase k (between marks k and k + 1)
+        if (!on) return;
+        GPRX_HIP(hipStreamSynchronize(s));
+        for (int k = 0; k < n && k + 1 < (int)ev.size(); k++) {
+            float t = 0;
+            (void)hipEventElapsedTime(&t, ev[k], ev[k + 1]);
+            ms[k] = t;
+        }
+    }
+    ~PhaseClock() {
+        for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+    }
+};
 
 // R = K(Xq, X) (qp x np, ld qp, zero padding), then R L^{-T} in place.  K(Xq, X) as MFMA pair
 // statistics (kcross_mma_kernel: the predict path's features of the queries and of the training
@@ -48,7 +84,7 @@ gprx_status model_predict(gprx_model* M, const void* Xq, int64_t q, void* mean, 
 // featV (the second side of a pair call).
 template <typename T>
 static void solve_rows_for(gprx_model* M, const T* dXq, const T* dtabQ, int64_t q, int64_t qp, T* R,
-                           bool feat_ready = false) {
+                           bool feat_ready = false, PhaseClock* pc = nullptr) {
     hipStream_t s = M->ctx->stream;
     const KCanon<T>& K = kcanon<T>(M);
     const int64_t npf = round_up(M->n, GT);
@@ -68,7 +104,9 @@ static void solve_rows_for(gprx_model* M, const T* dXq, const T* dtabQ, int64_t 
         launch_kbuild<T>(K, dXq, dtabQ, q, M->X.as<T>(), M->tab.as<T>(), M->n, M->d, R, qp, 0, false, T(0),
                          M->flag.as<int>(), s);
     }
+    if (pc) pc->mark();  // (the cross build | the row solve)
     trsm_rows<T>(M->A.as<T>(), M->ld, M->np, M->Linv.as<T>(), R, qp, qp, s);
+    if (pc) pc->mark();
 }
 
 // operator()(x, y) / GetCredibleInterval (lib/GaussianProcess.cpp:84-114) on a SHARDED fit:
@@ -538,6 +576,149 @@ gprx_status model_loo(gprx_model* M, uint32_t flags, double* value, void* mean, 
 }
 
 // ---------------------------------------------------------------------------------------
+// The joint posterior over q query points and draws from it (k_sample.hip; not in the reference).
+//   Sigma = K(Xq, Xq) [+ s^2 I] - R R^T,  R = K(Xq, X) L^{-T}  (solve_rows_for: the variance call's
+//   rows), built lower and identity-padded to 128 exactly as gprx_model_append builds its block S;
+//   a draw is mean + Lq z with Lq Lq^T = Sigma + j I (potrf_tiles on a copy, the strict upper part
+//   zeroed, one launch_gemm_nt over all nsamp m columns of normals).
+// The jitter j: the caller's, used once; or q eps max_p k(x_p, x_p) -- the scale of the
+// factorisation's own backward error -- times 10 for every non-positive pivot met, refused with
+// NOT_SPD once past 1e-2 max k.  A fitted model is read, never changed: everything lives in the
+// ps* buffers, R in pvRa.
+// ---------------------------------------------------------------------------------------
+static void require_joint(gprx_model* M, const char* who) {
+    gprx_ctx* ctx = M->ctx;
+    const std::string w(who);
+    GPRX_REQUIRE(!((ctx->hc && ctx->world > 1) || ctx->virt), GPRX_ERR_STATE,
+                 w + ": sharded contexts (multi-rank or virtual-rank) are not supported");
+    GPRX_REQUIRE(!M->sparse_cov, GPRX_ERR_STATE, w + ": a sparse-covariance model holds no factor");
+    GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE, w + ": a caller-evaluated kernel has no device form to build K(Xq, Xq) with");
+    GPRX_REQUIRE(M->fitted && M->has_alpha, GPRX_ERR_STATE, w + ": gaussian process is not initialized.");
+    GPRX_REQUIRE(!M->dist_fitted, GPRX_ERR_STATE, w + ": the model was fitted sharded");
+    GPRX_REQUIRE(M->method == 0, GPRX_ERR_STATE, w + ": the model's factor is an LU (the joint posterior needs the Cholesky factor)");
+}
+
+// Sigma + diag I (lower, identity-padded to qp, ld qp) into psS; the cross rows in pvRa
+template <typename T>
+static void joint_cov(gprx_model* M, const Points<T>& Q, int64_t q, int64_t qp, T diag, PhaseClock& pc) {
+    hipStream_t s = M->ctx->stream;
+    const KCanon<T>& K = kcanon<T>(M);
+    M->pvRa.ensure(sizeof(T) * qp * M->np);
+    M->psS.ensure(sizeof(T) * qp * qp);
+    T* R = M->pvRa.as<T>();
+    T* S = M->psS.as<T>();
+    solve_rows_for<T>(M, Q.x, Q.tab, q, qp, R, false, &pc);
+    launch_kbuild<T>(K, Q.x, Q.tab, q, Q.x, Q.tab, q, M->d, S, qp, qp, true, diag, M->flag.as<int>(), s);
+    launch_gemm_nt<T>(S, qp, R, qp, R, qp, qp, qp, M->np, T(-1), T(1), true, s);
+    pc.mark();
+}
+
+template <typename T>
+gprx_status model_posterior(gprx_model* M, const void* Xq, int64_t q, uint32_t flags, void* mean, void* cov) {
+    require_joint(M, "gprx_model_posterior");
+    hipStream_t s = M->ctx->stream;
+    const int64_t qp = round_up(q, GT);
+    Points<T> Q;
+    stage_points<T>(Q, kcanon<T>(M), Xq, q, M->d, M->ctx->device, s, false);
+    if (mean) {
+        M->psVec.ensure(sizeof(T) * (q * M->m + q));
+        predict_staged<T>(M, Q, q, M->psVec.as<T>(), (T*)nullptr);
+        download(mean, M->psVec.p, sizeof(T) * q * M->m, s);
+    }
+    if (cov) {
+        PhaseClock pc(M->ctx);
+        const T sig = (T)M->sigma;
+        joint_cov<T>(M, Q, q, qp, (flags & GPRX_POST_NOISE) ? sig * sig : T(0), pc);
+        // the q x q block alone; with no padding it is one contiguous copy (a strided copy into
+        // pageable memory goes column by column: 128 MiB at Q = 4096)
+        if (qp == q) {
+            launch_sym_fill<T>(M->psS.as<T>(), qp, q, s);
+            download(cov, M->psS.p, sizeof(T) * q * q, s);
+        } else {
+            download_sym<T>(cov, M->psS, qp, q, s);
+        }
+    }
+    return GPRX_OK;
+}
+
+template <typename T>
+gprx_status model_sample(gprx_model* M, const void* Xq, int64_t q, int64_t nsamp, uint64_t seed, uint32_t flags,
+                         const void* z, double* jitter, void* out) {
+    require_joint(M, "gprx_model_sample");
+    gprx_ctx* ctx = M->ctx;
+    hipStream_t s = ctx->stream;
+    const KCanon<T>& K = kcanon<T>(M);
+    const int m = M->m;
+    const int64_t qp = round_up(q, GT), ncols = nsamp * m, ncp = round_up(ncols, GT);
+    Points<T> Q;
+    stage_points<T>(Q, K, Xq, q, M->d, ctx->device, s, false);
+    // every buffer before the first launch: a failed allocation leaves nothing half done
+    M->pvRa.ensure(sizeof(T) * qp * M->np);
+    M->psS.ensure(sizeof(T) * qp * qp);
+    M->psL.ensure(sizeof(T) * qp * qp);
+    M->psLinv.ensure(sizeof(T) * qp * DB);
+    M->psVec.ensure(sizeof(T) * (q * m + q));
+    M->psZ.ensure(sizeof(T) * ncols * q);
+    M->psZp.ensure(sizeof(T) * ncp * qp);
+    M->psOut.ensure(sizeof(T) * (qp * ncp + ncols * q));
+    if (z) {  // the caller's normals in the generator's place (host or device memory)
+        GPRX_HIP(hipStreamSynchronize(s));
+        GPRX_HIP(hipMemcpy(M->psZ.p, z, sizeof(T) * ncols * q, hipMemcpyDefault));
+    }
+    T* dmean = M->psVec.as<T>();
+    T* kqq = dmean + q * m;
+    predict_staged<T>(M, Q, q, dmean, (T*)nullptr);
+    // the prior diagonal's maximum: the scale of the jitter
+    launch_pair_kernel<T>(K, Q.x, Q.x, q, M->d, kqq, s);
+    std::vector<T> hk((size_t)q);
+    download(hk.data(), kqq, sizeof(T) * q, s);
+    double maxdiag = 0;
+    for (T v : hk) maxdiag = std::max(maxdiag, (double)v);
+    const bool automatic = !jitter || *jitter < 0;
+    double j = automatic ? (double)q * (double)std::numeric_limits<T>::epsilon() * maxdiag : *jitter;
+    const T sig = (T)M->sigma;
+    const T noise = (flags & GPRX_POST_NOISE) ? sig * sig : T(0);
+
+    launch_fit_status_init(M->info.as<int>(), M->flag.as<int>(), s);
+    PhaseClock pc(ctx);  // marks: start, cross build, row solve, rank update, factor, normals, transform
+    joint_cov<T>(M, Q, q, qp, noise + (T)j, pc);
+    T* S = M->psS.as<T>();
+    T* L = M->psL.as<T>();
+    for (;;) {  // factor a copy; the unfactored block stays for the next, larger jitter
+        GPRX_HIP(hipMemcpyAsync(L, S, sizeof(T) * qp * qp, hipMemcpyDeviceToDevice, s));
+        potrf_tiles<T>(L, qp, qp, qp, M->psLinv.as<T>(), M->info.as<int>(), ctx->ex);
+        int st[2];
+        download(&st[0], M->flag.p, sizeof(int), s);
+        download(&st[1], M->info.p, sizeof(int), s);
+        check_finite(st[0]);
+        check_sched(st[1]);
+        if (st[1] == INT_MAX) break;
+        const double jn = 10 * j;
+        if (!automatic || !(jn > j) || !(jn <= 1e-2 * maxdiag))
+            throw Error{GPRX_ERR_NOT_SPD, "gprx_model_sample: the joint covariance is not positive definite (jitter " +
+                                              std::to_string(j) + ")"};
+        launch_diag_fix<T>(S, qp, 0, q, q, (T)(jn - j), s);
+        launch_fit_status_init(M->info.as<int>(), M->flag.as<int>(), s);
+        j = jn;
+    }
+    pc.mark();
+    if (jitter) *jitter = j;
+    if (!z) launch_normals<T>(seed, ncols * q, M->psZ.as<T>(), s);
+    launch_stage_normals<T>(M->psZ.as<T>(), ncols, q, M->psZp.as<T>(), ncp, qp, s);
+    pc.mark();
+    // C (qp x ncp) = Lq Zp^T, then the mean added on the way into the (nsamp, q, m) layout
+    T* C = M->psOut.as<T>();
+    T* dout = C + qp * ncp;
+    launch_zero_upper<T>(L, qp, qp, s);
+    launch_gemm_nt<T>(C, qp, L, qp, M->psZp.as<T>(), ncp, qp, ncp, qp, T(1), T(0), false, s);
+    launch_sample_out<T>(C, qp, dmean, nsamp, q, m, dout, s);
+    pc.mark();
+    pc.read(M->psMs, 6);
+    download(out, dout, sizeof(T) * ncols * q, s);
+    return GPRX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // caller-evaluated kernels (k_hostk.hip): predict, posterior covariance and the LML gradient
 // from the caller's kernel vectors / derivative matrices
 // ---------------------------------------------------------------------------------------
@@ -628,6 +809,9 @@ gprx_status model_lml_dk(gprx_model* M, uint32_t flags, const void* dK, int32_t 
     template gprx_status model_core_matrix<T>(gprx_model*, void*);                                         \
     template gprx_status model_lml<T>(gprx_model*, uint32_t, double*, double*, int32_t*, double*);         \
     template gprx_status model_loo<T>(gprx_model*, uint32_t, double*, void*, void*, double*, int32_t*);    \
+    template gprx_status model_posterior<T>(gprx_model*, const void*, int64_t, uint32_t, void*, void*);    \
+    template gprx_status model_sample<T>(gprx_model*, const void*, int64_t, int64_t, uint64_t, uint32_t,   \
+                                         const void*, double*, void*);                                     \
     template gprx_status model_predict_kx<T>(gprx_model*, const void*, const void*, int64_t, void*, void*); \
     template gprx_status model_posterior_cov_kx<T>(gprx_model*, const void*, const void*, const void*,     \
                                                    int64_t, void*);                                        \

@@ -32,6 +32,7 @@ LML_COMPAT = 2
 LML_DISTRIBUTED = 4
 LML_FORCE_LU = 8
 LOO_GRAD = 1
+POST_NOISE = 1  # Model.posterior / Model.sample: the distribution of observations (sigma^2 on the diagonal)
 
 STATUS = {0: "OK", 1: "NONFINITE", 2: "NOT_SPD", 3: "SINGULAR", 4: "DIM", 5: "HIP", 6: "RCCL", 7: "OOM",
           8: "ARG", 9: "STATE", 10: "NO_DEVICE"}
@@ -50,6 +51,7 @@ EXPORTED = [
     "gprx_model_set_sparse_cov", "gprx_sparse_lml",
     "gprx_device_alloc", "gprx_device_free", "gprx_device_upload", "gprx_device_download",
     "gprx_model_append", "gprx_model_remove", "gprx_model_loo",
+    "gprx_model_posterior", "gprx_model_sample",
 ]
 
 
@@ -151,6 +153,11 @@ def lib():
         L.gprx_model_loo.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(ctypes.c_double),
                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                      ctypes.POINTER(ctypes.c_int32)]
+        L.gprx_model_posterior.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_uint32,
+                                           ctypes.c_void_p, ctypes.c_void_p]
+        L.gprx_model_sample.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                        ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p,
+                                        ctypes.POINTER(ctypes.c_double), ctypes.c_void_p]
         L.gprx_model_set_kernel_matrix.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_set_sparse_cov.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
         L.gprx_model_predict_kx.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
@@ -199,6 +206,8 @@ def lib():
         L.gprx_dev_factor_update_width.argtypes = []
         L.gprx_dev_panel_trace.restype = ctypes.c_int64
         L.gprx_dev_panel_trace.argtypes = [ctypes.c_void_p, ctypes.c_int64]
+        L.gprx_dev_normals.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p]
+        L.gprx_dev_sample_phases.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         _lib = L
     return _lib
 
@@ -524,6 +533,13 @@ class Context:
         nb = lib().gprx_dev_panel_trace(_ptr(t), max_blocks)
         return t[:max(nb, 0)].copy()
 
+    def normals(self, seed, count, dtype=np.float64):
+        """The first `count` numbers of the normal stream `seed` that Model.sample draws from
+        (gprx_dev_normals): Philox4x32-10 + Box-Muller, number e from counter block e >> 1."""
+        z = np.empty(int(count), np.dtype(dtype))
+        self._c(lib().gprx_dev_normals(self.h, _dt(dtype), int(seed) & (2 ** 64 - 1), int(count), _ptr(z)))
+        return z
+
     def cholesky(self, A):
         A = np.array(A, copy=True, order="C")
         info = ctypes.c_int32()
@@ -820,3 +836,42 @@ class Model:
         self._c(lib().gprx_model_loo(self.h, LOO_GRAD if grad else 0, ctypes.byref(v), _ptr(mean), _ptr(var),
                                      _ptr(g) if grad else None, ctypes.byref(npar)))
         return v.value, mean, var, (g[:npar.value].copy() if grad else None)
+
+    def posterior(self, Xq, noise=False):
+        """The joint posterior over the query points Xq (q x d) -> (mean, cov): the mean (q x m,
+        the bits of predict) and the full q x q covariance K(Xq, Xq) - K(Xq, X) (K + s^2 I)^{-1}
+        K(X, Xq), shared by the label columns (gprx_model_posterior).  noise=True adds s^2 to the
+        diagonal: the distribution of observations.  The model is read, never changed."""
+        Xq = np.ascontiguousarray(Xq, self.dtype).reshape(-1, self.d)
+        q = Xq.shape[0]
+        mean = np.empty((q, self.m), self.dtype)
+        cov = np.empty((q, q), self.dtype)
+        self._c(lib().gprx_model_posterior(self.h, _ptr(Xq), q, POST_NOISE if noise else 0, _ptr(mean), _ptr(cov)))
+        return mean, cov
+
+    def sample(self, Xq, n=1, seed=0, noise=False, z=None, jitter=None):
+        """n joint draws at the query points Xq -> (samples, jitter): samples (n x q x m) =
+        mean + Lq z with Lq the Cholesky factor of the joint covariance plus jitter I
+        (gprx_model_sample).  The normals come from the device generator keyed by `seed` (draw i
+        does not depend on n; Context.normals returns the stream), or from z (n x m x q).  jitter:
+        None is automatic (q eps max k(x, x), escalated by 10 while the factorisation fails); a
+        value >= 0 is used as it is.  The jitter applied comes back."""
+        Xq = np.ascontiguousarray(Xq, self.dtype).reshape(-1, self.d)
+        q, n = Xq.shape[0], int(n)
+        if z is not None:
+            z = np.ascontiguousarray(z, self.dtype)
+            if z.size != n * self.m * q:
+                raise ValueError("sample: z holds n x m x q normals")
+        out = np.empty((n, q, self.m), self.dtype)
+        j = ctypes.c_double(-1.0 if jitter is None else float(jitter))
+        self._c(lib().gprx_model_sample(self.h, _ptr(Xq), q, n, int(seed) & (2 ** 64 - 1),
+                                        POST_NOISE if noise else 0, _ptr(z), ctypes.byref(j), _ptr(out)))
+        return out, (j.value if q and n else 0.0)
+
+    def sample_phases(self):
+        """Device ms of the last sample() call's phases, recorded while the context's statistics are
+        on (gprx_dev_sample_phases)."""
+        keys = ["cross_build", "row_solve", "rank_update", "factor", "normals", "transform"]
+        v = (ctypes.c_double * len(keys))()
+        self._c(lib().gprx_dev_sample_phases(self.h, v))
+        return dict(zip(keys, list(v)))

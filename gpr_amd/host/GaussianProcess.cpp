@@ -316,6 +316,51 @@ T GaussianProcess<T>::LeaveOneOut(MatrixType& mean, VectorType& variance) {
     return (T)value;
 }
 
+// the points xs as one q x d row-major block
+template <class T>
+static std::vector<T> PackPoints(const std::vector<DenseVector<T>>& xs, unsigned d, const char* who) {
+    std::vector<T> X(xs.size() * (std::size_t)d);
+    for (std::size_t a = 0; a < xs.size(); a++) {
+        if (xs[a].size() != d) throw std::string(who) + ": dimension of an input vector does not match the GP's";
+        for (unsigned k = 0; k < d; k++) X[a * d + k] = xs[a][k];
+    }
+    return X;
+}
+
+template <class T>
+void GaussianProcess<T>::GetPosterior(const std::vector<VectorType>& xs, MatrixType& mean, MatrixType& cov, bool noise) {
+    Initialize();
+    const std::vector<T> X = PackPoints<T>(xs, m_InputDimension, "GaussianProcess::GetPosterior");
+    std::lock_guard<std::mutex> lk(m_DevMu);
+    EnsureFactor();
+    if (m_HostKernel) throw std::string("GaussianProcess::GetPosterior: a kernel with no device form is not supported");
+    const std::size_t q = xs.size();
+    mean.resize(q, m_OutputDimension);
+    cov.resize(q, q);
+    ThrowIfFailed(gprx_model_posterior(m_Model, X.data(), (int64_t)q, noise ? GPRX_POST_NOISE : 0u, mean.data(), cov.data()),
+                  DefaultContext());
+}
+
+template <class T>
+std::vector<typename GaussianProcess<T>::MatrixType> GaussianProcess<T>::Sample(const std::vector<VectorType>& xs,
+                                                                                std::size_t nsamples, uint64_t seed,
+                                                                                bool noise) {
+    Initialize();
+    const std::vector<T> X = PackPoints<T>(xs, m_InputDimension, "GaussianProcess::Sample");
+    std::lock_guard<std::mutex> lk(m_DevMu);
+    EnsureFactor();
+    if (m_HostKernel) throw std::string("GaussianProcess::Sample: a kernel with no device form is not supported");
+    const std::size_t q = xs.size(), m = m_OutputDimension;
+    std::vector<T> out(nsamples * q * m);
+    double jitter = -1;  // automatic
+    ThrowIfFailed(gprx_model_sample(m_Model, X.data(), (int64_t)q, (int64_t)nsamples, seed, noise ? GPRX_POST_NOISE : 0u,
+                                    nullptr, &jitter, out.data()),
+                  DefaultContext());
+    std::vector<MatrixType> draws(nsamples, MatrixType(q, m));
+    for (std::size_t i = 0; i < nsamples; i++) std::copy(out.begin() + i * q * m, out.begin() + (i + 1) * q * m, draws[i].data());
+    return draws;
+}
+
 // lib/GaussianProcess.cpp:54-61
 template <class T>
 typename GaussianProcess<T>::VectorType GaussianProcess<T>::Predict(const VectorType& x) {

@@ -130,6 +130,17 @@ public:
     // without refitting.  Returns the predictive log probability summed over the outputs.
     TScalarType LeaveOneOut(MatrixType& mean, VectorType& variance);
 
+    // The JOINT posterior over the points xs (gprx_model_posterior; not in the reference, whose
+    // operator() gives one pair): mean (q x m, what Predict returns per point) and the full q x q
+    // covariance, from the device's Cholesky factor without refitting.  noise: sigma^2 added to the
+    // diagonal (the distribution of observations instead of the latent function).
+    void GetPosterior(const std::vector<VectorType>& xs, MatrixType& mean, MatrixType& cov, bool noise = false);
+    // nsamples joint draws at xs (gprx_model_sample): each a q x m matrix, mean + Lq z with Lq the
+    // Cholesky factor of that covariance (plus the automatic jitter) and z from the device's
+    // counter-based normal generator keyed by `seed`; draw i does not depend on nsamples.
+    std::vector<MatrixType> Sample(const std::vector<VectorType>& xs, std::size_t nsamples, uint64_t seed,
+                                   bool noise = false);
+
 protected:
     KernelTypePointer m_Kernel;
     TScalarType m_Sigma;

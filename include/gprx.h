@@ -334,6 +334,31 @@ gprx_status gprx_model_lml(gprx_model* model, uint32_t flags, double* value, dou
 gprx_status gprx_model_loo(gprx_model* model, uint32_t flags, double* value, void* mean, void* var, double* grad,
                            int32_t* nparams);
 
+#define GPRX_POST_NOISE 1u /* add sigma^2 to the diagonal: the distribution of observations, not of the latent function */
+/* The JOINT posterior over q query points (not in the reference, whose operator() gives one pair at
+ * a time): mean (q x m, or NULL; the same bits as gprx_model_predict) and the full covariance
+ *   Sigma = K(Xq, Xq) - K(Xq, X) (K + sigma^2 I)^{-1} K(X, Xq)   (q x q, symmetric, or NULL),
+ * shared by all label columns, from the Cholesky factor: K(Xq, Xq) - R R^T, R = K(Xq, X) L^{-T}.
+ * Only the q x q block crosses to the host.  The model is read, never changed (append / remove
+ * leave it servable as it stands).  q = 0 writes nothing.
+ * GPRX_ERR_STATE, model untouched: an unfitted model, an LU factor, a sharded fit or a multi-rank /
+ * virtual-rank context, a sparse-covariance model, a caller-evaluated kernel.  GPRX_ERR_OOM: the
+ * workspace could not be allocated (the model stays fitted). */
+gprx_status gprx_model_posterior(gprx_model* model, const void* Xq, int64_t q, uint32_t flags, void* mean, void* cov);
+/* nsamp draws from that joint posterior: out[i, p, c] (nsamp x q x m) = mean[p, c] + sum_r Lq[p, r]
+ * z[(i m + c) q + r], Lq the lower Cholesky factor of Sigma + jitter I.
+ * z: NULL -- the normals come from the device generator, Philox4x32-10 + Box-Muller keyed by `seed`,
+ *   number e = (i m + c) q + p from counter block e >> 1 (the exact definition: DESIGN.md 4.4b), so
+ *   a draw depends on (seed, i, c, p, q) and not on nsamp; or nsamp x m x q normals of the caller's,
+ *   in the model's dtype, that order.
+ * jitter: in, *jitter >= 0 is used as it is, once (GPRX_ERR_NOT_SPD if the factorisation meets a
+ *   non-positive pivot); *jitter < 0 or a NULL pointer is automatic: q eps max_p k(x_p, x_p), times
+ *   10 per failed factorisation, GPRX_ERR_NOT_SPD once it would pass 1e-2 max_p k(x_p, x_p).  Out: the
+ *   value applied.
+ * States and errors as gprx_model_posterior; q = 0 or nsamp = 0 writes nothing. */
+gprx_status gprx_model_sample(gprx_model* model, const void* Xq, int64_t q, int64_t nsamp, uint64_t seed,
+                              uint32_t flags, const void* z, double* jitter, void* out);
+
 /* SparseGaussianProcess::operator()(x,y) = k(x,y) - Kx^T Kmm^{-1} Ky + Kx^T RM Ky
  * (include/SparseGaussianProcess.h:94-106) on a model whose data are the inducing points:
  * W = Kmm^{-1} - RM (M x M, row-major, from gprx_sparse_fit) becomes resident, and

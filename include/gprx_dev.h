@@ -128,6 +128,13 @@ int64_t gprx_dev_panel_trace(int64_t* times, int64_t max_blocks);
 gprx_status gprx_dev_factor_update(gprx_ctx* ctx, gprx_dtype dtype, const void* L, int64_t n, const void* X, int32_t r,
                                    void* Lout, void* LinvOut);
 int32_t gprx_dev_factor_update_width(void);
+/* The normal generator of gprx_model_sample alone (k_sample.hip): the first `count` numbers of the
+ * stream `seed` in `dtype`, to host memory. */
+gprx_status gprx_dev_normals(gprx_ctx* ctx, gprx_dtype dtype, uint64_t seed, int64_t count, void* out_host);
+/* Device ms of the phases of the model's last gprx_model_sample made with the context's statistics
+ * on (gprx_ctx_set_stats; zeros otherwise): ms[0] cross build K(Xq, X), [1] row solve, [2] K(Xq, Xq)
+ * and the rank update, [3] factorisation (every attempt), [4] normals and their staging, [5] transform. */
+gprx_status gprx_dev_sample_phases(gprx_model* model, double* ms);
 #ifdef __cplusplus
 }
 #endif
