@@ -148,16 +148,23 @@ gprx_status gprx_model_set_data(gprx_model* M, const void* X, const void* Y, int
             return false;
         },
         [&] {
+            GPRX_REQUIRE(!M->scaled() || (int32_t)M->ell.size() == d, GPRX_ERR_DIM,
+                         "gprx_model_set_data: the input dimension differs from the number of length scales set");
             const size_t es = esize(M->dt);
             M->X.ensure(es * n * d);
             M->Y.ensure(es * n * m);
+            if (M->scaled()) M->Xraw.ensure(es * n * d);
             M->trim_posterior_workspace();
             // host or device memory (include/gprx.h conventions: a gprx_device_alloc pointer too)
-            GPRX_HIP(hipMemcpy(M->X.p, X, es * n * d, hipMemcpyDefault));
+            GPRX_HIP(hipMemcpy(M->scaled() ? M->Xraw.p : M->X.p, X, es * n * d, hipMemcpyDefault));
             GPRX_HIP(hipMemcpy(M->Y.p, Y, es * n * m, hipMemcpyDefault));
             M->n = n;
             M->d = d;
             M->m = m;
+            if (M->scaled()) {  // X = the scaled points, Xraw = the points as uploaded
+                by_dtype(M->dt, [&](auto t) { scale_model_rows<decltype(t)>(M, 0, n); });
+                GPRX_HIP(hipStreamSynchronize(M->ctx->stream));
+            }
             M->has_data = true;
             M->drop_sparse_cov();
             M->drop_fit();
@@ -190,6 +197,60 @@ gprx_status gprx_model_set_noise(gprx_model* M, double sigma) {
         M->sigma = sigma;
         M->drop_fit();
         return GPRX_OK;
+    });
+}
+
+gprx_status gprx_model_set_length_scales(gprx_model* M, const double* ell, int32_t d) {
+    return model_call(M, d >= 0, "gprx_model_set_length_scales: NULL model or negative d", CALL_DEVICE, [&] {
+        const bool clear = !ell || d == 0;
+        if (!clear) {
+            for (int j = 0; j < d; j++)
+                GPRX_REQUIRE(std::isfinite(ell[j]) && ell[j] > 0 &&
+                                 (M->dt == GPRX_F64 || (std::isfinite((float)ell[j]) && (float)ell[j] > 0)),
+                             GPRX_ERR_ARG, "gprx_model_set_length_scales: every length scale must be finite and > 0");
+            GPRX_REQUIRE(!M->has_data || d == M->d, GPRX_ERR_DIM,
+                         "gprx_model_set_length_scales: the number of length scales differs from the input dimension");
+            GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE,
+                         "gprx_model_set_length_scales: a caller-evaluated kernel owns its own metric");
+        }
+        if (clear && !M->scaled()) return GPRX_OK;  // (nothing set, nothing to clear: the fit stays)
+        hipStream_t s = M->ctx->stream;
+        const size_t es = esize(M->dt);
+        const size_t xb = M->has_data ? es * M->n * M->d : 0;
+        GPRX_HIP(hipStreamSynchronize(s));
+        // Xraw = the points as uploaded, whichever way the model goes
+        if (!M->scaled() && xb) {
+            M->Xraw.ensure(xb);
+            GPRX_HIP(hipMemcpy(M->Xraw.p, M->X.p, xb, hipMemcpyDeviceToDevice));
+        }
+        if (clear) {
+            if (xb) GPRX_HIP(hipMemcpy(M->X.p, M->Xraw.p, xb, hipMemcpyDeviceToDevice));
+            M->ell.clear();
+            M->Xraw.release();
+            M->rmXraw.release();
+        } else {
+            M->ell.assign(ell, ell + d);
+            M->ellT.ensure(es * d);
+            if (M->dt == GPRX_F64) {
+                GPRX_HIP(hipMemcpy(M->ellT.p, ell, sizeof(double) * d, hipMemcpyHostToDevice));
+            } else {
+                std::vector<float> ef(ell, ell + d);  // narrowed to T first
+                GPRX_HIP(hipMemcpy(M->ellT.p, ef.data(), sizeof(float) * d, hipMemcpyHostToDevice));
+            }
+            if (xb) {
+                by_dtype(M->dt, [&](auto t) { scale_model_rows<decltype(t)>(M, 0, M->n); });
+                GPRX_HIP(hipStreamSynchronize(s));
+            }
+        }
+        M->drop_sparse_cov();
+        M->drop_fit();
+        return GPRX_OK;
+    });
+}
+
+gprx_status gprx_model_lml_scale_grad(gprx_model* M, double* grad_ell) {
+    return model_call(M, grad_ell, "gprx_model_lml_scale_grad: NULL argument", CALL_PROF | CALL_DEVICE, [&] {
+        return by_dtype(M->dt, [&](auto t) { return model_lml_scale_grad<decltype(t)>(M, grad_ell); });
     });
 }
 
@@ -365,6 +426,9 @@ gprx_status gprx_model_set_sparse_cov(gprx_model* M, const void* W) {
 gprx_status gprx_model_set_kernel_matrix(gprx_model* M, const void* K) {
     return model_call(M, K, "gprx_model_set_kernel_matrix: NULL argument", 0, [&] {
         GPRX_REQUIRE(M->has_data, GPRX_ERR_STATE, "gprx_model_set_kernel_matrix: set the data first");
+        GPRX_REQUIRE(!M->scaled(), GPRX_ERR_STATE,
+                     "gprx_model_set_kernel_matrix: the model has length scales set (a caller-evaluated kernel owns "
+                     "its own metric: clear them first)");
         GPRX_HIP(hipSetDevice(M->ctx->device));
         const size_t es = esize(M->dt);
         M->Kext.ensure(es * M->n * M->n);

@@ -577,7 +577,14 @@ gprx_status model_append(gprx_model* M, const void* Xnew, const void* Ynew, int6
     grow_keep(M->X, sizeof(T) * n1 * d, sizeof(T) * n * d, s);
     grow_keep(M->Y, sizeof(T) * n1 * m, sizeof(T) * n * m, s);
     GPRX_HIP(hipStreamSynchronize(s));
-    GPRX_HIP(hipMemcpy(M->X.as<T>() + n * d, Xnew, sizeof(T) * k * d, hipMemcpyDefault));
+    if (M->scaled()) {  // the new rows as uploaded behind Xraw's, scaled into X
+        grow_keep(M->Xraw, sizeof(T) * n1 * d, sizeof(T) * n * d, s);
+        GPRX_HIP(hipMemcpy(M->Xraw.as<T>() + n * d, Xnew, sizeof(T) * k * d, hipMemcpyDefault));
+        scale_model_rows<T>(M, n, k);
+        GPRX_HIP(hipStreamSynchronize(s));
+    } else {
+        GPRX_HIP(hipMemcpy(M->X.as<T>() + n * d, Xnew, sizeof(T) * k * d, hipMemcpyDefault));
+    }
     GPRX_HIP(hipMemcpy(M->Y.as<T>() + n * m, Ynew, sizeof(T) * k * m, hipMemcpyDefault));
     // full refit of the extended data: the factor is the LU (a forced LU stays one), or the
     // trailing Cholesky below met a non-positive pivot
@@ -774,10 +781,12 @@ gprx_status model_remove(gprx_model* M, int64_t first, int64_t count, uint32_t f
     };
     compact(M->X, M->rmX, d);
     compact(M->Y, M->rmY, m);
+    if (M->scaled()) compact(M->Xraw, M->rmXraw, d);  // (the points as uploaded move with the scaled ones)
     auto refit = [&](uint32_t fl) {  // full refit of the reduced data
         GPRX_HIP(hipStreamSynchronize(s));
         swap_buf(M->X, M->rmX);
         swap_buf(M->Y, M->rmY);
+        if (M->scaled()) swap_buf(M->Xraw, M->rmXraw);
         M->n = n1;
         M->drop_fit();
         return model_fit<T>(M, fl, out);
@@ -830,6 +839,7 @@ gprx_status model_remove(gprx_model* M, int64_t first, int64_t count, uint32_t f
     swap_buf(M->Linv, M->rmLinv);
     swap_buf(M->X, M->rmX);
     swap_buf(M->Y, M->rmY);
+    if (M->scaled()) swap_buf(M->Xraw, M->rmXraw);
     swap_buf(M->alpha, M->apAlpha);
     M->n = n1;
     M->np = np1;

@@ -794,6 +794,27 @@ void launch_loo_vectors(const T* alpha, const T* Y, int64_t n, int64_t np, int m
 template <typename T>
 void launch_loo_weights(const T* C, int64_t ldc, int64_t np, const T* sw, const T* r, T* B, double* part, T* a,
                         hipStream_t s);
+// ---- per-dimension length scales (k_ard.hip) --------------------------------------------
+// out[i, j] = in[i, j] / ell[j] (n x d, row-major; in == out allowed): the model's scaled points
+template <typename T>
+void launch_scale_points(const T* in, const T* ell, int64_t n, int d, T* out, hipStream_t s);
+// der[p, j, c] /= ell[j] (q x d x m): the scaled-space derivative back to d/dx
+template <typename T>
+void launch_unscale_deriv(T* der, const T* ell, int64_t q, int d, int m, hipStream_t s);
+// whether the length-scale gradient takes the tree: r2 leaves only (no Periodic leaf), any terms
+template <typename T>
+bool ard_grad_supported(const KCanon<T>& K);
+// doubles of launch_ard_grad's partials for nf feature rows and d dimensions
+int64_t ard_part_elems(int64_t nf, int d);
+// gout[j] = sum_{a >= b} w_ab (x2 off the diagonal) dk/dr2(a, b) (z_aj - z_bj)^2, j < d, with
+// w_ab = (alpha_a beta_b + alpha_b beta_a) / 2 - C_ab (lower triangle of C, ldc), z the centred
+// points as the U features hold them (FU, FV: launch_pair_features, nf rows).  part:
+// ard_part_elems doubles; the tiles' partials are reduced in a fixed order.
+template <typename T>
+void launch_ard_grad(const KCanon<T>& K, const KCanon<T>* Kd, const T* FU, const T* FV, int64_t nf, int64_t n, int d,
+                     const T* alpha, const T* beta, const T* C, int64_t ldc, double* part, double* gout,
+                     hipStream_t s);
+
 // ---- posterior sampling (k_sample.hip) --------------------------------------------------
 // out[e] = the normal number e of the stream `seed` (Philox4x32-10 + Box-Muller, computed in fp64,
 // rounded once to T), e < count; a value depends on (seed, e) alone

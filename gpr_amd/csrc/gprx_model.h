@@ -260,6 +260,14 @@ struct gprx_model {
     // operator()(x,y) = k(x,y) - Kx^T W Ky (include/SparseGaussianProcess.h:94-106)
     bool sparse_cov = false;
     gprx::DevBuf sparseW;
+    // per-dimension length scales (gprx_model_set_length_scales; empty: none).  With scales X holds
+    // the SCALED points Xs = Xraw / (T)ell -- what every consumer of the model's points reads, so
+    // none of them changes -- and Xraw the points as uploaded (rmXraw: gprx_model_remove's second
+    // buffer of them); ellT is ell narrowed to T on the device.  Without scales X is the data as
+    // uploaded and Xraw is not used.  ardPart: gprx_model_lml_scale_grad's partials and result.
+    std::vector<double> ell;
+    gprx::DevBuf Xraw, rmXraw, ellT, ardPart;
+    bool scaled() const { return !ell.empty(); }
     std::mutex mu;
     ~gprx_model() { gprx::dist_engine_free(dist_engine); }
 
@@ -271,6 +279,7 @@ struct gprx_model {
     //   set_data           sparse_cov, fit                        (has_data)
     //   set_kernel         sparse_cov, fit                        (has_kernel; host_k off)
     //   set_kernel_matrix  sparse_cov, fit                        (has_kernel; host_k on)
+    //   set_length_scales  sparse_cov, fit                        (ell; X rescaled from Xraw)
     //   set_noise          fit                                    -
     //   set_alpha          -                                      has_alpha (the factor stays)
     //   set_sparse_cov     -                                      sparse_cov
@@ -378,6 +387,12 @@ inline KCanon<float>& kcanon<float>(gprx_model* m) {
     return m->kf;
 }
 
+// the model's length scales in T on the device, nullptr without scales (stage_points' ell)
+template <typename T>
+const T* model_ell(const gprx_model* m) {
+    return m->scaled() ? m->ellT.as<T>() : nullptr;
+}
+
 // ---------------------------------------------------------------------------------------
 // transfers
 // ---------------------------------------------------------------------------------------
@@ -463,14 +478,17 @@ struct Points {  // a set of points on the device with what the kernels read of 
 // n points of the caller's (n x d, row-major) on the device, with their tables.  accept_device:
 // device memory of this GPU is read where it lies (dev_input); otherwise the points are always
 // copied (upload), so the staged set never aliases memory the caller may overwrite.
+// ell (a model's length scales in T on the device, or nullptr): the staged copy is divided by them,
+// as the model's own points are (never with accept_device: the copy is written).
 template <typename T>
 void stage_points(Points<T>& P, const KCanon<T>& K, const void* p, int64_t n, int d, int device, hipStream_t s,
-                  bool accept_device) {
-    if (accept_device) {
+                  bool accept_device, const T* ell = nullptr) {
+    if (accept_device && !ell) {
         P.x = dev_input<T>(P.xbuf, p, sizeof(T) * n * d, device, s);
     } else {
         upload<T>(P.xbuf, p, sizeof(T) * n * d, s);
         P.x = P.xbuf.template as<T>();
+        if (ell && n > 0) launch_scale_points<T>(P.x, ell, n, d, P.xbuf.template as<T>(), s);
     }
     P.n = n;
     P.tab = sincos_tables<T>(K, P.x, n, d, P.tabbuf, s);
@@ -490,6 +508,13 @@ void train_features(gprx_model* M, bool v_side, int64_t np) {
     DevBuf& f = v_side ? M->featV : M->featU;
     f.ensure(sizeof(T) * np * pairs_feature_cols<T>(K, M->d));
     launch_pair_features<T>(K, M->X.as<T>(), M->n, M->d, M->X.as<T>(), v_side, f.as<T>(), np, M->ctx->stream);
+}
+
+// a model with length scales: rows [row0, row0 + rows) of X = those rows of Xraw / (T)ell
+template <typename T>
+void scale_model_rows(gprx_model* M, int64_t row0, int64_t rows) {
+    launch_scale_points<T>(M->Xraw.as<T>() + row0 * M->d, M->ellT.as<T>(), rows, M->d, M->X.as<T>() + row0 * M->d,
+                           M->ctx->stream);
 }
 
 // pair features of q query points against the model's samples (same centre), qp rows apart
@@ -529,6 +554,8 @@ gprx_status model_lml(gprx_model* M, uint32_t flags, double* value, double* grad
 template <typename T>
 gprx_status model_loo(gprx_model* M, uint32_t flags, double* value, void* mean, void* var, double* grad,
                       int32_t* nparams);
+template <typename T>
+gprx_status model_lml_scale_grad(gprx_model* M, double* grad_ell);
 template <typename T>
 gprx_status model_posterior(gprx_model* M, const void* Xq, int64_t q, uint32_t flags, void* mean, void* cov);
 template <typename T>

@@ -38,10 +38,12 @@ gprx_status model_predict(gprx_model* M, const void* Xq, int64_t q, void* mean, 
     const int d = M->d, m = M->m;
     Points<T> Q;
     DevBuf dmean, dder;
-    stage_points<T>(Q, kcanon<T>(M), Xq, q, d, M->ctx->device, s, false);
+    stage_points<T>(Q, kcanon<T>(M), Xq, q, d, M->ctx->device, s, false, model_ell<T>(M));
     dmean.ensure(sizeof(T) * q * m);
     if (deriv) dder.ensure(sizeof(T) * q * d * m);
     predict_staged<T>(M, Q, q, dmean.as<T>(), deriv ? dder.as<T>() : nullptr);
+    // with length scales the kernels differentiate in the scaled space: d/dx_j = (d/dz_j) / ell_j
+    if (deriv && M->scaled()) launch_unscale_deriv<T>(dder.as<T>(), model_ell<T>(M), q, d, m, s);
     download(mean, dmean.p, sizeof(T) * q * m, s);
     if (deriv) download(deriv, dder.p, sizeof(T) * q * d * m, s);
     return GPRX_OK;
@@ -193,6 +195,10 @@ static gprx_status model_posterior_cov_dist_core(gprx_model* M, const void* Xa, 
     Points<T> Zc;  // one chunk's query columns
     upload<T>(da, Xa, sizeof(T) * q * d, s);
     upload<T>(db, Xb, sizeof(T) * q * d, s);
+    if (M->scaled()) {  // the prior pairs in the model's metric, as the staged chunks below
+        launch_scale_points<T>(da.as<T>(), model_ell<T>(M), q, d, da.as<T>(), s);
+        launch_scale_points<T>(db.as<T>(), model_ell<T>(M), q, d, db.as<T>(), s);
+    }
     kab.ensure(sizeof(T) * q);
     launch_pair_kernel<T>(K, da.as<T>(), db.as<T>(), q, d, kab.as<T>(), s);
     std::vector<T> hk((size_t)q), res((size_t)q);
@@ -208,7 +214,7 @@ static gprx_status model_posterior_cov_dist_core(gprx_model* M, const void* Xa, 
             std::memcpy(&Z[(size_t)(c * DB + jj) * d], xa + (p0 + j) * d, sizeof(T) * d);
             if (!same) std::memcpy(&Z[(size_t)(c * DB + DB / 2 + jj) * d], xb + (p0 + j) * d, sizeof(T) * d);
         }
-        stage_points<T>(Zc, K, Z.data(), nq, d, M->ctx->device, s, false);
+        stage_points<T>(Zc, K, Z.data(), nq, d, M->ctx->device, s, false, model_ell<T>(M));
         dist_posterior<T>(M->dist_engine, K, M->X.as<T>(), K.nper > 0 ? M->tab.as<T>() : nullptr, M->n, d, Zc.x, Zc.tab,
                           nch, !same, sum, s);
         for (int64_t j = 0; j < cnt; j++) res[p0 + j] = (T)((double)hk[p0 + j] - sum[(j / per) * DB + j % per]);
@@ -237,8 +243,8 @@ gprx_status model_posterior_cov(gprx_model* M, const void* Xa, const void* Xb, i
     const int64_t qp = round_up(q, GT);
     Points<T> Pa, Pb;
     DevBuf Ra, Rb, kab, res;
-    stage_points<T>(Pa, K, Xa, q, d, M->ctx->device, s, false);
-    stage_points<T>(Pb, K, Xb, q, d, M->ctx->device, s, false);
+    stage_points<T>(Pa, K, Xa, q, d, M->ctx->device, s, false, model_ell<T>(M));
+    stage_points<T>(Pb, K, Xb, q, d, M->ctx->device, s, false, model_ell<T>(M));
     if (M->sparse_cov) {  // k(x,y) - Kx^T W Ky over the inducing points, batched on the device
         const int64_t Mp = round_up(M->n, GT);
         DevBuf Z;
@@ -576,6 +582,69 @@ gprx_status model_loo(gprx_model* M, uint32_t flags, double* value, void* mean, 
 }
 
 // ---------------------------------------------------------------------------------------
+// d LML / d ell of a model with length scales (k_ard.hip; not in the reference): -(1 / ell_j) times
+// the pair sum g_j = sum_{a != b} (alpha_a alpha_b - C_ab) dk/dr2 (z_aj - z_bj)^2 over the model's
+// scaled points.  A model fitted by Cholesky is read as gprx_model_loo reads it (C formed from the
+// factor when it is not resident); the call's own buffer is ardPart (the tiles' partials, then g).
+// ---------------------------------------------------------------------------------------
+template <typename T>
+gprx_status model_lml_scale_grad(gprx_model* M, double* grad_ell) {
+    gprx_ctx* ctx = M->ctx;
+    GPRX_REQUIRE(M->scaled(), GPRX_ERR_STATE, "gprx_model_lml_scale_grad: no length scales are set");
+    GPRX_REQUIRE(!((ctx->hc && ctx->world > 1) || ctx->virt), GPRX_ERR_STATE,
+                 "gprx_model_lml_scale_grad: sharded contexts (multi-rank or virtual-rank) are not supported");
+    GPRX_REQUIRE(!M->sparse_cov, GPRX_ERR_STATE, "gprx_model_lml_scale_grad: a sparse-covariance model holds no factor");
+    GPRX_REQUIRE(!M->host_k, GPRX_ERR_STATE, "gprx_model_lml_scale_grad: a caller-evaluated kernel owns its own metric");
+    GPRX_REQUIRE(M->fitted || (M->has_data && M->has_kernel), GPRX_ERR_STATE,
+                 "gprx_model_lml_scale_grad: set the data, the kernel and the noise first");
+    GPRX_REQUIRE(!(M->fitted && M->dist_fitted), GPRX_ERR_STATE, "gprx_model_lml_scale_grad: the model was fitted sharded");
+    GPRX_REQUIRE(!(M->fitted && M->method == 1), GPRX_ERR_STATE,
+                 "gprx_model_lml_scale_grad: the model's factor is an LU (the gradient needs the Cholesky factor)");
+    const KCanon<T>& K = kcanon<T>(M);
+    GPRX_REQUIRE(K.nper == 0, GPRX_ERR_STATE,
+                 "gprx_model_lml_scale_grad: trees with a Periodic leaf are not supported (their values are)");
+    GPRX_REQUIRE(M->m == 1, GPRX_ERR_DIM, "gprx_model_lml_scale_grad: only one output dimension is supported, as gprx_model_lml");
+    const int d = M->d;
+    if (!K.need_r2) {  // White leaves only: nothing depends on the metric off the diagonal
+        for (int j = 0; j < d; j++) grad_ell[j] = 0.0;
+        return GPRX_OK;
+    }
+    if (!M->fitted) {  // data, kernel and noise but no fit: fitted here, the inverse riding along
+        M->want_inv = true;
+        gprx_status st;
+        try {
+            st = model_fit<T>(M, GPRX_FIT_NO_LU_FALLBACK, nullptr);
+        } catch (...) {
+            M->want_inv = false;
+            throw;
+        }
+        M->want_inv = false;
+        if (st != GPRX_OK) return st;
+    }
+    hipStream_t s = ctx->stream;
+    if (!M->inv_ready) {
+        model_inverse<T>(M);
+        M->inverse_done();
+    }
+    const int64_t n = M->n, npf = round_up(n, GT);
+    train_features<T>(M, false, npf);
+    train_features<T>(M, true, npf);
+    const KCanon<T>* kdev = M->kfit.put(K, s);
+    const int64_t pe = ard_part_elems(npf, d);
+    M->ardPart.ensure(sizeof(double) * (pe + d));
+    double* g = M->ardPart.as<double>() + pe;
+    launch_ard_grad<T>(K, kdev, M->featU.as<T>(), M->featV.as<T>(), npf, n, d, M->alpha.as<T>(), M->alpha.as<T>(),
+                       M->C.as<T>(), M->np, M->ardPart.as<double>(), g, s);
+    download(grad_ell, g, sizeof(double) * d, s);
+    for (int j = 0; j < d; j++) {
+        if (!std::isfinite(grad_ell[j]))
+            throw Error{GPRX_ERR_NONFINITE, "gprx_model_lml_scale_grad: the gradient is not finite."};
+        grad_ell[j] = -grad_ell[j] / (double)(T)M->ell[j];
+    }
+    return GPRX_OK;
+}
+
+// ---------------------------------------------------------------------------------------
 // The joint posterior over q query points and draws from it (k_sample.hip; not in the reference).
 //   Sigma = K(Xq, Xq) [+ s^2 I] - R R^T,  R = K(Xq, X) L^{-T}  (solve_rows_for: the variance call's
 //   rows), built lower and identity-padded to 128 exactly as gprx_model_append builds its block S;
@@ -619,7 +688,7 @@ gprx_status model_posterior(gprx_model* M, const void* Xq, int64_t q, uint32_t f
     hipStream_t s = M->ctx->stream;
     const int64_t qp = round_up(q, GT);
     Points<T> Q;
-    stage_points<T>(Q, kcanon<T>(M), Xq, q, M->d, M->ctx->device, s, false);
+    stage_points<T>(Q, kcanon<T>(M), Xq, q, M->d, M->ctx->device, s, false, model_ell<T>(M));
     if (mean) {
         M->psVec.ensure(sizeof(T) * (q * M->m + q));
         predict_staged<T>(M, Q, q, M->psVec.as<T>(), (T*)nullptr);
@@ -651,7 +720,7 @@ gprx_status model_sample(gprx_model* M, const void* Xq, int64_t q, int64_t nsamp
     const int m = M->m;
     const int64_t qp = round_up(q, GT), ncols = nsamp * m, ncp = round_up(ncols, GT);
     Points<T> Q;
-    stage_points<T>(Q, K, Xq, q, M->d, ctx->device, s, false);
+    stage_points<T>(Q, K, Xq, q, M->d, ctx->device, s, false, model_ell<T>(M));
     // every buffer before the first launch: a failed allocation leaves nothing half done
     M->pvRa.ensure(sizeof(T) * qp * M->np);
     M->psS.ensure(sizeof(T) * qp * qp);
@@ -809,6 +878,7 @@ gprx_status model_lml_dk(gprx_model* M, uint32_t flags, const void* dK, int32_t 
     template gprx_status model_core_matrix<T>(gprx_model*, void*);                                         \
     template gprx_status model_lml<T>(gprx_model*, uint32_t, double*, double*, int32_t*, double*);         \
     template gprx_status model_loo<T>(gprx_model*, uint32_t, double*, void*, void*, double*, int32_t*);    \
+    template gprx_status model_lml_scale_grad<T>(gprx_model*, double*);                                    \
     template gprx_status model_posterior<T>(gprx_model*, const void*, int64_t, uint32_t, void*, void*);    \
     template gprx_status model_sample<T>(gprx_model*, const void*, int64_t, int64_t, uint64_t, uint32_t,   \
                                          const void*, double*, void*);                                     \

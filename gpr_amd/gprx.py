@@ -52,6 +52,7 @@ EXPORTED = [
     "gprx_device_alloc", "gprx_device_free", "gprx_device_upload", "gprx_device_download",
     "gprx_model_append", "gprx_model_remove", "gprx_model_loo",
     "gprx_model_posterior", "gprx_model_sample",
+    "gprx_model_set_length_scales", "gprx_model_lml_scale_grad",
 ]
 
 
@@ -136,6 +137,8 @@ def lib():
                                           ctypes.c_int32, ctypes.c_int32]
         L.gprx_model_set_kernel.argtypes = [ctypes.c_void_p, ctypes.POINTER(KernelDesc)]
         L.gprx_model_set_noise.argtypes = [ctypes.c_void_p, ctypes.c_double]
+        L.gprx_model_set_length_scales.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.c_int32]
+        L.gprx_model_lml_scale_grad.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
         L.gprx_model_fit.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.POINTER(FitInfo)]
         L.gprx_model_append.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                         ctypes.c_uint32, ctypes.POINTER(FitInfo)]
@@ -610,6 +613,7 @@ class Model:
         self.n = self.d = self.m = 0
         self.kernel = None
         self._Xh = None
+        self.length_scales = None  # per-dimension length scales (set_length_scales), or None
 
     def close(self):
         if self.h:
@@ -678,6 +682,28 @@ class Model:
 
     def set_noise(self, sigma):
         self._c(lib().gprx_model_set_noise(self.h, float(sigma)))
+
+    def set_length_scales(self, ell):
+        """Per-dimension length scales (gprx_model_set_length_scales): the model's kernel becomes
+        k_tree(x / ell, y / ell), the division done once in the model's dtype with ell narrowed to
+        it first, so the model equals one without scales on `X / ell.astype(dtype)`.  None clears
+        them.  Drops the fit, as set_kernel."""
+        if ell is None:
+            self._c(lib().gprx_model_set_length_scales(self.h, None, 0))
+            self.length_scales = None
+            return
+        e = np.ascontiguousarray(np.asarray(ell, np.float64).reshape(-1))
+        self._c(lib().gprx_model_set_length_scales(self.h, e.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                   e.shape[0]))
+        self.length_scales = e.copy()
+
+    def lml_scale_grad(self):
+        """d LML / d ell (gprx_model_lml_scale_grad) -> ndarray (d,): the gradient of lml()'s value
+        in the length scales, from the fitted model as it stands (an unfitted one is fitted first)."""
+        d = self.d if self.length_scales is None else self.length_scales.shape[0]
+        g = np.zeros(max(d, 1), np.float64)
+        self._c(lib().gprx_model_lml_scale_grad(self.h, g.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return g[:d].copy()
 
     def fit(self, flags=FIT_DEFAULT):
         info = FitInfo()
@@ -802,7 +828,12 @@ class Model:
         self._c(lib().gprx_model_core_matrix(self.h, _ptr(C)))
         return C
 
-    def lml(self, grad=True, compat=False, distributed=False, force_lu=False):
+    def lml(self, grad=True, compat=False, distributed=False, force_lu=False, scales=False):
+        """-> (value, grad, logdet); with scales=True -> (value, grad, logdet, grad_ell), the
+        length-scale gradient (lml_scale_grad) from the same fit."""
+        if scales:
+            out = self.lml(grad=grad, compat=compat, distributed=distributed, force_lu=force_lu)
+            return out + (self.lml_scale_grad(),)
         flags = ((LML_GRAD if grad else 0) | (LML_COMPAT if compat else 0) | (LML_DISTRIBUTED if distributed else 0)
                  | (LML_FORCE_LU if force_lu else 0))
         if self._host_kernel():

@@ -109,6 +109,12 @@ template <class T>
 void GaussianProcess<T>::UploadState() {
     gprx_ctx* ctx = DefaultContext();
     const std::size_t n = m_SampleVectors.size();
+    if (!m_ScalesUploaded) {  // before the data: the device checks the count against the dimension
+        std::vector<double> ell(m_LengthScales.size());
+        for (std::size_t k = 0; k < ell.size(); k++) ell[k] = (double)m_LengthScales[k];
+        ThrowIfFailed(gprx_model_set_length_scales(Model(), ell.empty() ? nullptr : ell.data(), (int32_t)ell.size()), ctx);
+        m_ScalesUploaded = true;
+    }
     if (!m_DataUploaded || !m_Model || m_DeviceSamples != n || !m_PendingRemovals.empty()) {
         m_PendingRemovals.clear();
         const std::size_t d = m_InputDimension, m = m_OutputDimension;
@@ -466,6 +472,9 @@ std::vector<T> GaussianProcess<T>::CredibleIntervalBatch(const MatrixType& Xq) {
 template <class T>
 void GaussianProcess<T>::Save(std::string prefix) {
     if (!m_Initialized) throw std::string("GaussianProcess::Save: gaussian process is not initialized.");
+    if (m_LengthScales.size() > 0)
+        throw std::string("GaussianProcess::Save: the gaussian process has length scales, which the file format "
+                          "cannot hold (clear them with SetLengthScales, or save them beside the files)");
     WriteMatrix<MatrixType>(m_RegressionVectors, prefix + "-RegressionVectors.txt");
     if (m_EfficientStorage) {  // :152 drops the in-memory core matrix as well
         m_CoreMatrix.resize(0, 0);

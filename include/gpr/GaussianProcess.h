@@ -106,6 +106,19 @@ public:
         m_Sigma = sigma;
         m_Initialized = false;
     }
+    // Per-dimension length scales (gprx_model_set_length_scales; not in the reference, whose kernels
+    // are isotropic): the GP's kernel becomes k(x / ell, y / ell), one metric for every leaf of the
+    // kernel tree.  An empty vector clears them.  Checked against the input dimension (and refused for
+    // a kernel with no device form) when the state next goes to the device.  Save refuses a GP with
+    // length scales: the reference's five files have no place for them.
+    void SetLengthScales(const VectorType& ell) {
+        m_LengthScales = ell;
+        m_ScalesUploaded = false;
+        m_Initialized = false;
+        m_DeviceFactor = false;
+        m_FitCholesky = false;
+    }
+    const VectorType& GetLengthScales() const { return m_LengthScales; }
     virtual unsigned GetNumberOfInputDimensions() const { return m_InputDimension; }
     virtual void SetInversionMethod(InversionMethod m) { m_InvMethod = m; }
     virtual InversionMethod GetInversionMethod() { return m_InvMethod; }
@@ -167,6 +180,8 @@ protected:
                                   // they are here: an optimiser loop re-evaluating the likelihood
                                   // under new kernel parameters re-sends only the kernel, and
                                   // Update() only the samples added since
+    VectorType m_LengthScales;        // per-dimension length scales, empty: none
+    bool m_ScalesUploaded = true;     // the device model holds m_LengthScales (UploadState sends them)
     std::size_t m_DeviceSamples = 0;  // samples resident on the device (UploadState re-sends all
                                       // of them when it differs from the sample count)
     // RemoveSample calls on device-resident samples since the device data was last in step: the

@@ -111,6 +111,23 @@ protected:
         e.grad.resize(grad ? np : 0);
         return e;
     }
+    // d LML / d ell on the gp's current samples/kernel/noise/length scales (gprx_model_lml_scale_grad,
+    // which fits); the same bookkeeping as Evaluate.
+    VectorType EvaluateLengthScaleDerivatives(const GaussianProcessTypePointer gp) const {
+        std::lock_guard<std::mutex> lk(gp->m_DevMu);
+        gp->UploadState();
+        std::vector<double> g(gp->m_LengthScales.size());
+        if (g.empty()) throw std::string("GaussianLogLikelihood::GetLengthScaleDerivatives: the gp has no length scales");
+        ThrowIfFailed(gprx_model_lml_scale_grad(gp->m_Model, g.data()), DefaultContext());
+        gp->m_DeviceFactor = true;
+        gp->m_FitCholesky = false;  // (as Evaluate: not a factor Update() may extend)
+        gp->m_CoreValid = false;
+        if (gp->m_Initialized && gp->m_RegressionVectors.rows() == gp->m_SampleVectors.size())
+            ThrowIfFailed(gprx_model_set_alpha(gp->m_Model, gp->m_RegressionVectors.data()), DefaultContext());
+        VectorType out(g.size());
+        for (std::size_t j = 0; j < g.size(); j++) out[j] = (TScalarType)g[j];
+        return out;
+    }
 };
 
 // include/Likelihood.h:94-150: exp(data fit) / sqrt(det) / (2 pi)^{N/2}
@@ -175,6 +192,12 @@ public:
         MatrixType J(1, g.size());
         for (std::size_t p = 0; p < g.size(); p++) J(0, p) = g[p];
         return std::make_pair(Value(e), J);
+    }
+    // d LML / d ell_j of a gp with length scales (GaussianProcess::SetLengthScales; not in the
+    // reference): the gradient of operator()'s exact value in the length scales, from one device
+    // fit (gprx_model_lml_scale_grad).  One output dimension, a device kernel without Periodic leaves.
+    VectorType GetLengthScaleDerivatives(const GaussianProcessTypePointer gp) const {
+        return this->EvaluateLengthScaleDerivatives(gp);
     }
     virtual std::string ToString() const { return "GaussianLogLikelihood"; }
 

@@ -191,6 +191,23 @@ gprx_status gprx_model_set_data(gprx_model* model, const void* X, const void* Y,
 gprx_status gprx_model_set_kernel(gprx_model* model, const gprx_kernel_desc* kernel);
 /* SetSigma (include/GaussianProcess.h:140-143): noise standard deviation. */
 gprx_status gprx_model_set_noise(gprx_model* model, double sigma);
+/* Per-dimension length scales (automatic relevance determination; not in the reference): with
+ * ell set the model's kernel is k(x, y) = k_tree(x / ell, y / ell), element-wise, one metric
+ * shared by every leaf of the tree.  The leaves keep their own sigma, so a common factor of ell
+ * and the sigmas is redundant: the caller resolves it (e.g. sigma = 1 in every leaf).
+ * The model keeps the scaled copy Xs[i, j] = X[i, j] / (T)ell[j] beside X -- ONE division in the
+ * model's type T, ell narrowed to T first -- and every model call reads Xs; query points are
+ * scaled the same way, so a model with scales on X gives the same bits as a model without on
+ * X / ell computed that way.  gprx_model_predict's derivative is d/dx (the scaled-space
+ * derivative divided by ell_j).  ell == NULL or d == 0 clears the metric.
+ * Drops what gprx_model_set_kernel drops (the sparse covariance and the fit).
+ * GPRX_ERR_ARG: an ell[j] that is not finite and > 0.  GPRX_ERR_DIM: d differs from the data's
+ * (from this call or from gprx_model_set_data, whichever comes second).  GPRX_ERR_STATE: the
+ * model has a caller-evaluated kernel (gprx_model_set_kernel_matrix; that call refuses a model
+ * with scales likewise): the caller's kernel owns its metric.
+ * The context-level entry points below (gprx_kernel_matrix, gprx_cross_matrix, gprx_deriv_matrix,
+ * gprx_sparse_fit, gprx_sparse_lml) take no model and stay isotropic: their callers pre-scale. */
+gprx_status gprx_model_set_length_scales(gprx_model* model, const double* ell, int32_t d);
 
 #define GPRX_FIT_DEFAULT 0u
 #define GPRX_FIT_NO_LU_FALLBACK 1u /* report NOT_SPD instead of refactoring with LU.  By default a
@@ -314,6 +331,18 @@ gprx_status gprx_model_core_matrix(gprx_model* model, void* C);
  * grad may be NULL; nparams receives the kernel's parameter count. */
 gprx_status gprx_model_lml(gprx_model* model, uint32_t flags, double* value, double* grad, int32_t* nparams,
                            double* logdet);
+
+/* d LML / d ell_j, j < d, of a model with length scales (gprx_model_set_length_scales): the
+ * value and convention of gprx_model_lml, whose value's central difference in ell_j it reproduces:
+ *   grad_ell_j = 1/2 sum_ab (alpha_a alpha_b - C_ab) dK_ab/d ell_j,
+ *   dK_ab/d ell_j = -(2 / ell_j) dk/dr2(a, b) (z_aj - z_bj)^2,  z = x / ell.
+ * A model fitted by Cholesky is read as it is (C is formed from the factor if it is not
+ * resident, as gprx_model_loo with GPRX_LOO_GRAD); an unfitted one is fitted first, the inverse
+ * riding along (GPRX_FIT_NO_LU_FALLBACK).  Two calls return the same bits.
+ * GPRX_ERR_DIM: m != 1.  GPRX_ERR_STATE, model untouched: no scales set, an LU factor, a sharded
+ * fit or a multi-rank / virtual-rank context, a sparse-covariance model, a caller-evaluated
+ * kernel, a tree with a Periodic leaf (its values all work with scales). */
+gprx_status gprx_model_lml_scale_grad(gprx_model* model, double* grad_ell /* d doubles */);
 
 #define GPRX_LOO_GRAD 1u /* also compute the hyper-parameter gradient */
 /* Leave-one-out cross-validation (Rasmussen & Williams, GPML 5.4.2; not in the reference).  With
