@@ -24,7 +24,7 @@ int* Exec::scratch_ints(size_t n) {
     if (n > scratch_n) {
         if (scratch) GPRX_HIP(hipFree(scratch));
         scratch = nullptr;
-        GPRX_HIP(hipMalloc(&scratch, sizeof(int) * n));
+        GPRX_HIP(dev_malloc(&scratch, sizeof(int) * n));
         scratch_n = n;
     }
     return scratch;
@@ -546,7 +546,7 @@ gprx_status gprx_device_alloc(gprx_ctx* ctx, int64_t bytes, void** out) {
     if (bytes == 0) return GPRX_OK;
     void* p = nullptr;
     GPRX_HIP(hipSetDevice(ctx->device));
-    const hipError_t e = hipMalloc(&p, (size_t)bytes);
+    const hipError_t e = dev_malloc(&p, (size_t)bytes);
     if (e != hipSuccess)
         throw Error{GPRX_ERR_OOM, std::string("gprx_device_alloc: hipMalloc: ") + hipGetErrorString(e)};
     *out = p;

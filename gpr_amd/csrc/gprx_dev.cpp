@@ -41,7 +41,7 @@ static gprx_status bench_impl(int what, int64_t M, int64_t N, int64_t K, int ite
     std::vector<void*> bufs;
     auto alloc = [&](size_t b) {
         void* p = nullptr;
-        if (hipMalloc(&p, b) != hipSuccess) throw Error{GPRX_ERR_OOM, "dev bench: hipMalloc failed"};
+        if (dev_malloc(&p, b) != hipSuccess) throw Error{GPRX_ERR_OOM, "dev bench: hipMalloc failed"};
         bufs.push_back(p);
         return p;
     };
@@ -176,10 +176,10 @@ static gprx_status forward_panel_impl(const void* Lh, int64_t n, void* Rh, int r
     gprx_status st = GPRX_OK;
     std::string msg;
     try {
-        GPRX_HIP(hipMalloc(&dA, sizeof(T) * hA.size()));
-        GPRX_HIP(hipMalloc(&dLi, sizeof(T) * hLi.size()));
-        GPRX_HIP(hipMalloc(&dR, sizeof(T) * hR.size()));
-        GPRX_HIP(hipMalloc(&dinfo, sizeof(int)));
+        GPRX_HIP(dev_malloc(&dA, sizeof(T) * hA.size()));
+        GPRX_HIP(dev_malloc(&dLi, sizeof(T) * hLi.size()));
+        GPRX_HIP(dev_malloc(&dR, sizeof(T) * hR.size()));
+        GPRX_HIP(dev_malloc(&dinfo, sizeof(int)));
         GPRX_HIP(hipStreamSynchronize(s));
         GPRX_HIP(hipMemcpy(dA, hA.data(), sizeof(T) * hA.size(), hipMemcpyHostToDevice));
         GPRX_HIP(hipMemcpy(dLi, hLi.data(), sizeof(T) * hLi.size(), hipMemcpyHostToDevice));
@@ -247,12 +247,12 @@ static gprx_status factor_update_impl(const void* Lh, int64_t n, const void* Xh,
     gprx_status st = GPRX_OK;
     std::string msg;
     try {
-        GPRX_HIP(hipMalloc(&dA, sizeof(T) * hA.size()));
-        GPRX_HIP(hipMalloc(&dX, sizeof(T) * hX.size()));
-        GPRX_HIP(hipMalloc(&dO, sizeof(T) * hO.size()));
-        GPRX_HIP(hipMalloc(&dLi, sizeof(T) * hLi.size()));
-        GPRX_HIP(hipMalloc(&dW, sizeof(T) * factor_update_ws_elems(nb, r)));
-        GPRX_HIP(hipMalloc(&dinfo, sizeof(int)));
+        GPRX_HIP(dev_malloc(&dA, sizeof(T) * hA.size()));
+        GPRX_HIP(dev_malloc(&dX, sizeof(T) * hX.size()));
+        GPRX_HIP(dev_malloc(&dO, sizeof(T) * hO.size()));
+        GPRX_HIP(dev_malloc(&dLi, sizeof(T) * hLi.size()));
+        GPRX_HIP(dev_malloc(&dW, sizeof(T) * factor_update_ws_elems(nb, r)));
+        GPRX_HIP(dev_malloc(&dinfo, sizeof(int)));
         GPRX_HIP(hipStreamSynchronize(s));
         GPRX_HIP(hipMemcpy(dA, hA.data(), sizeof(T) * hA.size(), hipMemcpyHostToDevice));
         GPRX_HIP(hipMemcpy(dX, hX.data(), sizeof(T) * hX.size(), hipMemcpyHostToDevice));
@@ -368,7 +368,7 @@ extern "C" gprx_status gprx_dev_fexp(gprx_ctx* ctx, const double* x, int64_t n, 
     (void)ctx;
     if (n <= 0) return GPRX_OK;
     double *dx = nullptr, *dy = nullptr;
-    if (hipMalloc(&dx, sizeof(double) * n) != hipSuccess || hipMalloc(&dy, sizeof(double) * n) != hipSuccess)
+    if (dev_malloc(&dx, sizeof(double) * n) != hipSuccess || dev_malloc(&dy, sizeof(double) * n) != hipSuccess)
         return GPRX_ERR_OOM;
     (void)hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice);
     hipLaunchKernelGGL(dev_fexp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dx, n, dy);
@@ -387,8 +387,8 @@ extern "C" gprx_status gprx_dev_diag_factor(gprx_ctx* ctx, int32_t variant, cons
     long long* pr = nullptr;
     const size_t b = sizeof(double) * DB * DB;
     gprx_status st = GPRX_OK;
-    if (hipMalloc(&dA, b) != hipSuccess || hipMalloc(&dLi, b) != hipSuccess || hipMalloc(&di, sizeof(int)) != hipSuccess ||
-        hipMalloc(&pr, sizeof(long long) * 8) != hipSuccess) {
+    if (dev_malloc(&dA, b) != hipSuccess || dev_malloc(&dLi, b) != hipSuccess || dev_malloc(&di, sizeof(int)) != hipSuccess ||
+        dev_malloc(&pr, sizeof(long long) * 8) != hipSuccess) {
         st = GPRX_ERR_OOM;
     } else {
         const int big = 0x7fffffff;

@@ -67,14 +67,8 @@ struct DMem {
     void alloc(size_t b, bool fine) {
         release();
         if (b == 0) b = 256;
-        if (fine) GPRX_HIP(hipExtMallocWithFlags(&p, b, hipDeviceMallocFinegrained));
-        else GPRX_HIP(hipMalloc(&p, b));
+        GPRX_HIP(dev_malloc(&p, b, fine));  // (GPRX_POISON: filled and drained, as DevBuf -- gprx_alloc.h)
         bytes = b;
-        static const bool poison = std::getenv("GPRX_POISON") != nullptr;  // (debugging, as DevBuf)
-        if (poison) {  // (drained: the ranks' non-blocking streams do not wait for the null stream)
-            GPRX_HIP(hipMemset(p, 0x41, b));
-            GPRX_HIP(hipDeviceSynchronize());
-        }
     }
     void release() {
         if (p) (void)hipFree(p);
@@ -1264,14 +1258,22 @@ void dist_posterior(DistEngineBase* eng, const KCanon<T>& K, const T* X, const T
     // has no check, lib/GaussianProcess.cpp:684-693, and its operator() returns the NaN, as the
     // single-GPU path does; the flag the build raises is cleared here and by the next fit)
     GPRX_HIP(hipMemsetAsync(nfl, 0, sizeof(int), s));
-    GPRX_HIP(hipStreamSynchronize(s));
-    host_barrier(E);  // every rank's previous use of its window (a fit, an earlier batch) is over
-    E.vep++;
+    // every rank's partial sums sized and allocated BEFORE the first rank's launch: an allocation
+    // can block the host on the device (a grown buffer's hipFree; under GPRX_POISON the fill's
+    // drain) while an earlier rank's kernel already spins in its bounded wait for tiles a rank not
+    // yet launched would produce -- the wait then runs into its time limit
     for (auto& Rp : E.ranks) {
         DistRank<T>& Rk = *Rp;
         const size_t pb = sizeof(double) * std::max<size_t>(1, Rk.orows.size()) * (size_t)nq;
         if (Rk.pvpart.bytes < pb) Rk.pvpart.alloc(pb, false);
         if (Rk.pvsum.bytes < sizeof(double) * (size_t)nq) Rk.pvsum.alloc(sizeof(double) * (size_t)nq, false);
+    }
+    GPRX_HIP(hipStreamSynchronize(s));
+    host_barrier(E);  // every rank's previous use of its window (a fit, an earlier batch) is over
+    E.vep++;
+    // every rank's launch back to back, as the fit's: only stream-ordered calls in between
+    for (auto& Rp : E.ranks) {
+        DistRank<T>& Rk = *Rp;
         GPRX_HIP(hipMemsetAsync(Rk.sctl.p, 0, sizeof(int) * 8, Rk.s));
         GPRX_HIP(hipMemsetD32Async((hipDeviceptr_t)Rk.info.p, INT_MAX, 1, Rk.s));
         PVArgs<T> a;

@@ -24,6 +24,7 @@
 
 #include "../../include/gprx.h"
 #include "gprx_error.h"
+#include "gprx_alloc.h"
 
 namespace gprx {
 
@@ -664,7 +665,7 @@ struct BlockTrace {
     long long* ensure(int nb) {
         if (n < nb) {
             if (dev) GPRX_HIP(hipFree(dev));
-            GPRX_HIP(hipMalloc(&dev, sizeof(long long) * 4 * nb));
+            GPRX_HIP(dev_malloc(&dev, sizeof(long long) * 4 * nb));
         }
         n = nb;
         return dev;

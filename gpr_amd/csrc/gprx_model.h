@@ -40,17 +40,8 @@ struct DevBuf {
         if (b <= bytes && p) return;
         release();
         if (b == 0) return;
-        GPRX_HIP(hipMalloc(&p, b));
+        GPRX_HIP(dev_malloc(&p, b));  // (GPRX_POISON: filled with finite garbage, gprx_alloc.h)
         bytes = b;
-        // GPRX_POISON (debugging): fresh buffers hold finite garbage (bytes 0x41: 12.1f, 2.3e6),
-        // as reused memory does, so a read of unwritten memory shows in the results
-        static const bool poison = std::getenv("GPRX_POISON") != nullptr;
-        // (the fill runs on the null stream, which the context's non-blocking streams do not wait
-        // for: drained here, or it can land after the first kernel's stores into the new buffer)
-        if (poison) {
-            GPRX_HIP(hipMemset(p, 0x41, b));
-            GPRX_HIP(hipDeviceSynchronize());
-        }
     }
     void release() {
         if (p) (void)hipFree(p);

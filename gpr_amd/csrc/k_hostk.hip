@@ -127,7 +127,7 @@ void launch_dk_grad(const T* dK, int P, int64_t n, const T* alpha, const T* C, i
     if (P <= 0 || n <= 0) return;
     const unsigned gx = (unsigned)std::min<int64_t>(1024, (n * n + 255) / 256);
     double* part = nullptr;  // per-block slots (stream-ordered scratch)
-    GPRX_HIP(hipMallocAsync((void**)&part, sizeof(double) * gx * (size_t)P, s));
+    GPRX_HIP(dev_malloc_async(&part, sizeof(double) * gx * (size_t)P, s));
     hipLaunchKernelGGL(dk_grad_kernel<T>, dim3(gx, (unsigned)P), dim3(256), 0, s, dK, n, alpha, C, ldc, part);
     hipLaunchKernelGGL(dk_grad_sum_kernel, dim3((unsigned)P), dim3(256), 0, s, (const double*)part, (int)gx, out);
     GPRX_HIP(hipGetLastError());

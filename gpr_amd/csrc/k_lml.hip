@@ -316,7 +316,7 @@ struct GradSlots {
     double* p = nullptr;
     hipStream_t s;
     GradSlots(int64_t nblk, hipStream_t st) : s(st) {
-        GPRX_HIP(hipMallocAsync((void**)&p, sizeof(double) * MAX_LEAF * 3 * (size_t)std::max<int64_t>(nblk, 1), s));
+        GPRX_HIP(dev_malloc_async(&p, sizeof(double) * MAX_LEAF * 3 * (size_t)std::max<int64_t>(nblk, 1), s));
     }
     void finish(int nleaf, int64_t nblk, double* acc) {
         hipLaunchKernelGGL(lml_grad_sum_kernel, dim3((unsigned)(3 * nleaf)), dim3(256), 0, s, (const double*)p, nblk, acc);

@@ -197,7 +197,7 @@ template <typename T>
 void launch_rowdot(const T* Va, const T* Vb, int64_t ld, int64_t q, int64_t n, const T* kab, T* out, hipStream_t s) {
     if (q == 0) return;
     T* part = nullptr;
-    GPRX_HIP(hipMalloc((void**)&part, sizeof(T) * RD_SPLIT * q));
+    GPRX_HIP(dev_malloc(&part, sizeof(T) * RD_SPLIT * q));
     hipLaunchKernelGGL(rowdot_part_kernel<T>, dim3((unsigned)((q + 63) / 64), RD_SPLIT), dim3(256), 0, s, Va, Vb, ld,
                        q, n, part);
     hipLaunchKernelGGL(rowdot_sum_kernel<T>, dim3((unsigned)((q + 255) / 256)), dim3(256), 0, s, (const T*)part, q,

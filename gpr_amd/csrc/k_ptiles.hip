@@ -719,7 +719,7 @@ void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info
         d.n = (int64_t)S.list.size();
         d.est_us = S.est_us;
         d.ident_even = S.ident_even;
-        GPRX_HIP(hipMalloc(&d.list, sizeof(int4) * std::max<int64_t>(1, d.n)));
+        GPRX_HIP(dev_malloc(&d.list, sizeof(int4) * std::max<int64_t>(1, d.n)));
         GPRX_HIP(hipMemcpy(d.list, S.list.data(), sizeof(int4) * d.n, hipMemcpyHostToDevice));
         d.host = S.list;
         it = st.sched.emplace(key, d).first;
@@ -729,7 +729,7 @@ void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info
     if (st.ctr_ints < need) {
         if (st.ctr) GPRX_HIP(hipFree(st.ctr));
         st.ctr = nullptr;
-        GPRX_HIP(hipMalloc(&st.ctr, sizeof(int) * need));
+        GPRX_HIP(dev_malloc(&st.ctr, sizeof(int) * need));
         st.ctr_ints = need;
     }
     hipStream_t s = ex.s0;
@@ -764,12 +764,12 @@ void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info
     a.dist = nullptr;
     a.split = split ? 1 : 0;
     a.tflag = st.ctr + C_NCTL + nr + (size_t)nr * nc;
-    if (split && !st.pbuf) GPRX_HIP(hipMalloc(&st.pbuf, sizeof(T) * 4 * DB * DB));
+    if (split && !st.pbuf) GPRX_HIP(dev_malloc(&st.pbuf, sizeof(T) * 4 * DB * DB));
     a.pbuf = static_cast<T*>(st.pbuf);
     a.lab_rows = narrow ? lab_live : GT;
     if (fused) {
         GPRX_REQUIRE(build->nf == np, GPRX_ERR_ARG, "potrf_tiles: build features must have np rows");
-        if (!st.tb) GPRX_HIP(hipMalloc(&st.tb, sizeof(TileBuild<double>)));
+        if (!st.tb) GPRX_HIP(dev_malloc(&st.tb, sizeof(TileBuild<double>)));
         // (a pageable copy blocks the host until the stream reaches it: skipped when unchanged)
         const unsigned char* tbb = reinterpret_cast<const unsigned char*>(build);
         if (st.tb_last.size() != sizeof(TileBuild<T>) || std::memcmp(st.tb_last.data(), tbb, sizeof(TileBuild<T>)) != 0) {
@@ -785,7 +785,7 @@ void potrf_tiles(T* A, int64_t ld, int64_t np, int64_t nrows, T* Linv, int* info
     if (tracing) {
         if (st.trace_n + 7 * st.trace_nc < sd.n + 7 * nc) {  // + the split step's 5 nc stamp rows
             if (st.trace) GPRX_HIP(hipFree(st.trace));
-            GPRX_HIP(hipMalloc(&st.trace, sizeof(long long) * 4 * (sd.n + 7 * nc)));
+            GPRX_HIP(dev_malloc(&st.trace, sizeof(long long) * 4 * (sd.n + 7 * nc)));
         }
         st.trace_n = sd.n;
         st.trace_nc = nc;

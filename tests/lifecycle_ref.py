@@ -522,6 +522,8 @@ class Runner:
         T, _ = self.twin(fit_now=("fit", 0))
         self.M.set_alpha(T.alpha())
         mine = observe(self.M, st, self.dtype, ("pred",))
+        if self.collect is not None:
+            self.collect.update({f"{self.tag}{self.i}:installed:{k}": v for k, v in mine.items()})
         diff = self._bits(mine, observe(T, st, self.dtype, ("pred",)), "installed alpha: ")
         T.close()
         _, _, Xa, _ = queries(st.d, self.dtype)
@@ -574,12 +576,47 @@ def format_report(report, steps=None):
     return "\n".join(f"step {i}{' ' + steps[i]['op'] if steps else ''}: {what} ({detail})" for i, what, detail in report)
 
 
-def collect_reused(names, new_model, dtypes=(F64, F32)):
+# the scalar types each scenario runs in (test_gpu_lifecycle.py's own parametrisation)
+SCENARIO_DTYPES = {"a": (F64, F32), "b": (F64, F32), "c": (F64,), "d": (F64,), "e1": (F64, F32), "e2": (F64, F32),
+                   "f": (F64,), "g": (F32,), "h": (F64,), "i": (F64,)}
+UNSHARDED = ("a", "b", "c", "d", "e1", "e2", "f", "g", "i")  # scenario h needs a virtual-rank context
+
+
+def run_interleaved(new_model, dtype=F64, **kw):
+    """Scenario i: two models share the context's scratch (ticket and counter words, cached
+    schedules): fit M1, fit M2, observe M1, LML on M2 (its labels narrowed to one column first: the
+    likelihood takes m = 1), observe M1, observe M2.  Returns the two (closed) Runners."""
+    tag = kw.pop("tag", "")
+    r1, r2 = Runner(new_model, dtype, tag=tag + "M1/", **kw), Runner(new_model, dtype, tag=tag + "M2/", **kw)
+    s1, s2 = SCENARIOS["i1"], SCENARIOS["i2"]
+    try:
+        for step in s1[:3]:
+            r1.do(step)
+        for step in s2[:3]:
+            r2.do(step)
+        r1.observing = r2.observing = False
+        r1.do(s1[3])        # fit M1
+        r2.do(s2[3])        # fit M2
+        r1.compare()        # observe M1
+        r2.do(s2[4])
+        r2.do(s2[5])        # LML on M2
+        r1.compare()        # observe M1
+        r2.compare()        # observe M2
+    finally:
+        r1.close()
+        r2.close()
+    return r1, r2
+
+
+def collect_reused(names, new_model, dtypes=None, reads=None):
     """Every observation of the reused models of `names` (no twins, no oracle): what the poisoned
-    child process and its parent compare."""
+    child process and its parent compare.  dtypes: None = each scenario's own (SCENARIO_DTYPES);
+    reads: as Runner's (SHARDED_READS for scenario h, whose new_model makes models of a virtual-rank
+    context).  "i" is the interleaving of run_interleaved."""
     out = {}
     for name in names:
-        for dt in dtypes:
-            r = run_scenario(name, new_model, dt, twins=False, oracle=False, collect=out, tag=f"{name}/{np.dtype(dt).name}/")
-            assert not r.report, format_report(r.report)
+        for dt in (dtypes or SCENARIO_DTYPES[name]):
+            kw = dict(reads=reads, twins=False, oracle=False, collect=out, tag=f"{name}/{np.dtype(dt).name}/")
+            for r in (run_interleaved(new_model, dt, **kw) if name == "i" else [run_scenario(name, new_model, dt, **kw)]):
+                assert not r.report, format_report(r.report)
     return out

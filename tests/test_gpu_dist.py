@@ -328,6 +328,47 @@ def test_virtual_ranks_posterior_sharded(g, dtype):
         vctx.close()
 
 
+def test_virtual_ranks_posterior_growing_batch():
+    """The sharded posterior solve with a query batch that grows and shrinks on one model: q = 40
+    (one chunk of 128 columns), q = 128 + 77 (two chunks: every per-rank workspace of the solve
+    grows), q = 40 again (the larger workspace reused).  The ranks' partial-sum buffers are sized
+    before the first rank's launch: growing one between the launches frees the old buffer, which
+    can block the host while the rank already launched waits, bounded, for tiles of a rank not
+    yet launched.  Variances and pairs, each against the oracle at the tolerances of
+    test_virtual_ranks_posterior_sharded and bit for bit against a fresh model on the same
+    context that makes only that call.
+    n = 257: posterior_chunks >= 2 (asserted; needed for a batch to grow within one solve) already
+    holds at one row block, where rank 1 owns no matrix rows and nothing waits; at three row blocks
+    (rank 0 owns blocks 0 and 2, rank 1 block 1) each rank waits for the other's tiles, which is
+    the smallest shape at which the order of the launches matters."""
+    import gpr_amd
+    n, d, sigma = 257, 4, 0.5
+    X, Y = make_data(n, d, 1)
+    _, C_ref = O.fit(C3K, X, Y, sigma)
+    tol = TOL[np.dtype(np.float64)]
+    vctx = gpr_amd.Context(0, virtual=2)
+    try:
+        M, _ = _fit(vctx, C3K, X, Y, sigma, np.float64)
+        assert M.dist_info()["posterior_chunks"] >= 2
+        for q in (40, 128 + 77, 40):
+            Xa = make_queries(q, d)
+            for xb in (Xa, Xa[::-1].copy()):
+                c = M.posterior_cov(Xa, xb)
+                ref = O.posterior_cov(C3K, X, C_ref, Xa, xb)
+                kab = np.array([O.kernel_eval(C3K, a, b, with_grad=False) for a, b in zip(Xa, xb)])
+                err = float(np.max(np.abs(c - ref)))
+                print(f"growing batch q = {q}, {'variances' if xb is Xa else 'pairs'}: error {err:.2e}")
+                assert err <= tol * max(1.0, np.max(np.abs(kab)))
+                F, _ = _fit(vctx, C3K, X, Y, sigma, np.float64)
+                fresh = F.posterior_cov(Xa, xb)
+                F.close()
+                assert np.array_equal(c, fresh), f"q = {q}: differs from a fresh model, relerr {relerr(c, fresh):.2e}"
+        assert M.dist_info()["dense_factor"] == 0
+        M.close()
+    finally:
+        vctx.close()
+
+
 def test_virtual_ranks_small_window(monkeypatch):
     """A 2-panel window (GPRX_DIST_WINDOW) and single-panel update chunks over 3 ranks: every
     window slot is refilled many times, so the release protocol (a producer may overwrite slot

@@ -12,8 +12,8 @@ tests/lifecycle_ref.py drives one model through each scenario and, after every s
 it fitted, requires its reads (alpha, FitInfo, predict on both paths at q = 61 and 1, the
 posterior covariance of 40 equal and 40 reversed pairs, the core matrix) to be BIT-EQUAL to those
 of a twin -- a fresh model given only the current data, kernel, noise and the last refitting call
-(plus the appends after it) -- and to meet the oracle at the suite's tolerances.  The same
-scenarios also run in a child process with GPRX_POISON=1 (fresh device buffers hold finite
+(plus the appends after it) -- and to meet the oracle at the suite's tolerances.  Every scenario
+also runs in a child process with GPRX_POISON=1 (every fresh device allocation holds finite
 garbage instead of the zeros a new allocation usually has) and must give the same bits.
 """
 import os
@@ -103,46 +103,37 @@ def test_h_sharded_engine_reuse():
 def test_i_two_models_interleaved(ctx):
     """Two models share the context's scratch (ticket and counter words, cached schedules):
     fit M1, fit M2, observe M1, LML on M2 (its labels narrowed to one column first: the
-    likelihood takes m = 1), observe M1, observe M2."""
-    new = _models(ctx)
-    r1, r2 = L.Runner(new, np.float64), L.Runner(new, np.float64)
-    s1, s2 = L.SCENARIOS["i1"], L.SCENARIOS["i2"]
-    try:
-        for step in s1[:3]:
-            r1.do(step)
-        for step in s2[:3]:
-            r2.do(step)
-        r1.observing = r2.observing = False
-        r1.do(s1[3])        # fit M1
-        r2.do(s2[3])        # fit M2
-        r1.compare()        # observe M1
-        r2.do(s2[4])
-        r2.do(s2[5])        # LML on M2
-        r1.compare()        # observe M1
-        r2.compare()        # observe M2
-    finally:
-        r1.close()
-        r2.close()
+    likelihood takes m = 1), observe M1, observe M2 (lifecycle_ref.run_interleaved)."""
+    r1, r2 = L.run_interleaved(_models(ctx), np.float64)
     print(r1.summary("i/M1"))
     print(r2.summary("i/M2"))
     assert not r1.report, L.format_report(r1.report)
     assert not r2.report, L.format_report(r2.report)
 
 
+# argv: repository root, output file, "plain" | "sharded"
 _POISON_CHILD = r"""
 import sys
 import numpy as np
 sys.path.insert(0, sys.argv[1])
 import gpr_amd
 from tests import lifecycle_ref as L
-ctx = gpr_amd.Context(0)
-np.savez(sys.argv[2], **L.collect_reused(["a", "b"], lambda dtype: gpr_amd.Model(ctx, dtype)))
+if sys.argv[3] == "sharded":
+    ctx = gpr_amd.Context(0, virtual=2)
+    out = L.collect_reused(["h"], lambda dtype: gpr_amd.Model(ctx, dtype), reads=L.SHARDED_READS)
+else:
+    ctx = gpr_amd.Context(0)
+    out = L.collect_reused(L.UNSHARDED, lambda dtype: gpr_amd.Model(ctx, dtype))
+np.savez(sys.argv[2], **out)
+ctx.close()
 """
 
-# The same two scenarios (both dtypes, reused models only) take 0.10 s in this process, measured on
-# an MI355X with the library of the commit before these tests; the child also starts Python,
-# loads the code objects and plans its tile schedules, so its limit is rounded up generously.
-POISON_CHILD_TIMEOUT_S = 120
+# Limits of the two children: the whole child (Python start, code-object load, schedule planning,
+# the scenarios) run unpoisoned takes 0.80 s (scenarios a-g, i) and 0.52 s (scenario h), measured on
+# an MI355X with the library of the commit before these tests; times four for a shared machine
+# (3.2 s, 2.1 s), rounded up to half a minute (the start of a process on a busy machine varies by seconds).
+POISON_CHILD_TIMEOUT_S = 30
+POISON_SHARDED_CHILD_TIMEOUT_S = 30
 
 
 def _digest(a):
@@ -150,24 +141,45 @@ def _digest(a):
     return hashlib.sha1(np.ascontiguousarray(a).tobytes()).hexdigest()[:10]
 
 
-def test_poisoned_buffers_give_the_same_bits(ctx, tmp_path):
-    """Scenarios a and b in a child process with GPRX_POISON=1 (read once per process): every
-    fresh device buffer holds bytes 0x41 -- finite garbage, as reused memory does -- where a new
-    allocation is usually zero-filled, which is what hides a read of never-written padding from
-    the twin comparison.  Every observation must equal this process's unpoisoned run bit for bit.
-    (The words a wait could read are not at risk: the factorisation's ticket, counter and error
-    words live in context-owned memory that each launch initialises, and info / flag are set by
-    launch_fit_status_init before every fit; every wait is the bounded wait_until.)"""
-    import gpr_amd
+def _poisoned_child_equals(mine, mode, tmp_path, limit):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    f = tmp_path / "poisoned.npz"
-    r = subprocess.run([sys.executable, "-c", _POISON_CHILD, root, str(f)], env=dict(os.environ, GPRX_POISON="1"),
-                       capture_output=True, text=True, timeout=POISON_CHILD_TIMEOUT_S)
+    f = tmp_path / f"poisoned_{mode}.npz"
+    r = subprocess.run([sys.executable, "-c", _POISON_CHILD, root, str(f), mode], env=dict(os.environ, GPRX_POISON="1"),
+                       capture_output=True, text=True, timeout=limit)
     assert r.returncode == 0, r.stderr[-2000:]
-    mine = L.collect_reused(["a", "b"], lambda dtype: gpr_amd.Model(ctx, dtype))
     with np.load(f) as theirs:
         assert sorted(theirs.files) == sorted(mine)
         bad = [(k, f"relerr {L.relerr(mine[k], theirs[k]):.2e}", _digest(mine[k]), _digest(theirs[k]))
                for k in sorted(mine) if not np.array_equal(mine[k], theirs[k])]
     assert not bad, (f"{len(bad)} of {len(mine)} observations differ under GPRX_POISON "
                      f"(read, error, digest here, digest poisoned): {bad[:12]}")
+
+
+def test_poisoned_buffers_give_the_same_bits(ctx, tmp_path):
+    """Scenarios a to g and i (each in the scalar types of its own test above) in a child process
+    with GPRX_POISON=1 (read once per process): every fresh device allocation of the library holds
+    bytes 0x41 -- finite garbage, as reused memory does -- where a new allocation is usually
+    zero-filled, which is what hides a read of never-written padding from the twin comparison.
+    Every observation must equal this process's unpoisoned run bit for bit.
+    The control words are poisoned with everything else (gprx_alloc.h): Exec::scratch_ints, the
+    tile engine's counter block and the sharded engine's ctr / sctl / info / flag start as
+    0x41414141, and no launch may read one before its own initialisation wrote it.  DESIGN.md 3
+    ("Control words") lists, per buffer, the call that does: a memset or an init kernel on the
+    launch's stream ahead of every launch, never the allocation; every wait is the bounded
+    wait_until."""
+    import gpr_amd
+    mine = L.collect_reused(L.UNSHARDED, lambda dtype: gpr_amd.Model(ctx, dtype))
+    _poisoned_child_equals(mine, "plain", tmp_path, POISON_CHILD_TIMEOUT_S)
+
+
+def test_poisoned_sharded_engine_gives_the_same_bits(tmp_path):
+    """Scenario h (two virtual ranks, refits at n = 700, 260, 1536; alpha, predict and the sharded
+    posterior_cov) in a child of its own under GPRX_POISON=1: the ranks' storage, windows, mailboxes,
+    counter and flag words and the posterior solve's partial sums all start as bytes 0x41."""
+    import gpr_amd
+    vctx = gpr_amd.Context(0, virtual=2)
+    try:
+        mine = L.collect_reused(["h"], lambda dtype: gpr_amd.Model(vctx, dtype), reads=L.SHARDED_READS)
+    finally:
+        vctx.close()
+    _poisoned_child_equals(mine, "sharded", tmp_path, POISON_SHARDED_CHILD_TIMEOUT_S)

@@ -1,0 +1,93 @@
+"""Every library path outside the lifecycle scenarios under GPRX_POISON=1 (tests/poison_ref.py):
+the context-level entry points, the joint posterior and sampling after append and remove, the
+sparse fit and its likelihood, fp32 leave-one-out with its gradient, and the sharded engine's
+posterior covariance and LML gradient on two and three virtual ranks.
+
+GPRX_POISON fills every fresh device allocation of the library with bytes 0x41 (gprx_alloc.h: the
+models' and the sharded engine's buffers, the launches' counter and flag words, the tile engine's
+state, the stream-ordered partials, the caller's DeviceArrays).  It is read once per process, so
+the poisoned run is a child process; the child first proves that it is poisoned (a fresh
+DeviceArray reads back as 0x41), then every array must equal this process's unpoisoned run bit for
+bit.  The sharded cases run in a child of their own, so a failure there names itself."""
+import hashlib
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from tests import poison_ref as P
+from tests.helpers import relerr
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# argv: repository root, output file, "plain" | "sharded"
+_CHILD = r"""
+import sys
+import numpy as np
+sys.path.insert(0, sys.argv[1])
+import gpr_amd
+from tests import poison_ref as P
+ctx = gpr_amd.Context(0)
+assert P.is_poisoned(ctx), "GPRX_POISON=1 did not reach gprx_device_alloc: the comparison would prove nothing"
+if sys.argv[3] == "sharded":
+    vctx = {g: gpr_amd.Context(0, virtual=g) for g in P.VIRTUAL}
+    out = P.collect(None, vctx, P.SHARDED)
+    for c in vctx.values():
+        c.close()
+else:
+    out = P.collect(ctx, None, P.PLAIN)
+np.savez(sys.argv[2], **out)
+ctx.close()
+"""
+
+# Limits of the two children: the whole child (Python start, code-object load, schedule planning,
+# the cases) run unpoisoned takes 0.59 s (plain) and 0.85 s (sharded), measured on an MI355X with
+# this tree's library (the commit before these tests has no poisoned DeviceArray, and its sharded
+# posterior is what the fix here changes); times four for a shared machine (2.4 s, 3.4 s), rounded
+# up to half a minute (the start of a process on a busy machine varies by seconds).
+PLAIN_CHILD_TIMEOUT_S = 30
+SHARDED_CHILD_TIMEOUT_S = 30
+
+
+def _digest(a):
+    return hashlib.sha1(np.ascontiguousarray(a).tobytes()).hexdigest()[:10]
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+
+
+def _poisoned_child_equals(mine, mode, tmp_path, limit):
+    assert "GPRX_POISON" not in os.environ, "the reference side of the comparison is an unpoisoned run"
+    f = tmp_path / f"poisoned_{mode}.npz"
+    r = subprocess.run([sys.executable, "-c", _CHILD, ROOT, str(f), mode], env=dict(os.environ, GPRX_POISON="1"),
+                       capture_output=True, text=True, timeout=limit)
+    assert r.returncode == 0, r.stderr[-2000:]
+    with np.load(f) as theirs:
+        assert sorted(theirs.files) == sorted(mine)
+        bad = [(k, f"relerr {relerr(mine[k], theirs[k]):.2e}", _digest(mine[k]), _digest(theirs[k]))
+               for k in sorted(mine) if not _same_bits(mine[k], theirs[k])]
+    assert not bad, (f"{len(bad)} of {len(mine)} arrays differ under GPRX_POISON "
+                     f"(read, error, digest here, digest poisoned): {bad[:12]}")
+
+
+def test_plain_paths_give_the_same_bits_poisoned(ctx, tmp_path):
+    mine = P.collect(ctx, None, P.PLAIN)
+    print(f"poison: {len(mine)} arrays of the cases {', '.join(P.PLAIN)}")
+    _poisoned_child_equals(mine, "plain", tmp_path, PLAIN_CHILD_TIMEOUT_S)
+
+
+def test_sharded_paths_give_the_same_bits_poisoned(tmp_path):
+    import gpr_amd
+    vctx = {g: gpr_amd.Context(0, virtual=g) for g in P.VIRTUAL}
+    try:
+        mine = P.collect(None, vctx, P.SHARDED)
+    finally:
+        for c in vctx.values():
+            c.close()
+    print(f"poison: {len(mine)} arrays of the cases {', '.join(P.SHARDED)}")
+    _poisoned_child_equals(mine, "sharded", tmp_path, SHARDED_CHILD_TIMEOUT_S)
