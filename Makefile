@@ -18,7 +18,7 @@ HOST_HDRS := $(wildcard include/gpr/*.h) include/gprx.h
 CXXFLAGS  ?= -O2 -std=c++17 -fPIC -Wall -pthread -Iinclude
 CPPTESTS  := $(LIBDIR)/gp_host_test $(LIBDIR)/host_cpu_test $(LIBDIR)/gp_append_test $(LIBDIR)/pt_sched_test \
              $(LIBDIR)/matern_cpu_test $(LIBDIR)/gp_matern_test $(LIBDIR)/gp_remove_test $(LIBDIR)/loo_test \
-             $(LIBDIR)/sample_test $(LIBDIR)/ard_test
+             $(LIBDIR)/sample_test $(LIBDIR)/ard_test $(LIBDIR)/sparse_reuse_test
 
 all: $(LIBDIR)/libgprx.so $(LIBDIR)/libgpr_amd.so cpptests oracle
 

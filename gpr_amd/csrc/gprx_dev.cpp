@@ -10,6 +10,7 @@
 #include "../../include/gprx_dev.h"
 #include "gprx_model.h"
 #include "pt_sched.h"
+#include "sparse_plan.h"
 
 using namespace gprx;
 
@@ -355,6 +356,21 @@ extern "C" int64_t gprx_dev_schedule_list(int32_t nc, int32_t nr, int32_t P, int
         std::fprintf(stderr, "gprx_dev_schedule_list: %s\n", e.msg.c_str());
         return -1;
     }
+}
+
+extern "C" int32_t gprx_dev_sparse_clear_plan(int64_t* state, int64_t id, int64_t ld, int64_t cols, int64_t Mp,
+                                              int64_t M, int64_t nc, int64_t* rects) {
+    if (!state || !rects || M <= 0 || M > Mp || Mp > ld || nc < 0 || nc > cols) return -1;
+    gprx::SparseBlock st;
+    st.id = state[0], st.ld = state[1], st.cols = state[2], st.Mp = state[3], st.zero = state[4], st.rows = state[5];
+    gprx::ClearRect r[gprx::SPARSE_CLEAR_MAX];
+    const int k = gprx::sparse_clear_plan(st, id, ld, cols, Mp, M, nc, r);
+    for (int q = 0; q < k; q++) {
+        rects[4 * q] = r[q].row0, rects[4 * q + 1] = r[q].nrows;
+        rects[4 * q + 2] = r[q].col0, rects[4 * q + 3] = r[q].ncols;
+    }
+    state[0] = st.id, state[1] = st.ld, state[2] = st.cols, state[3] = st.Mp, state[4] = st.zero, state[5] = st.rows;
+    return k;
 }
 
 namespace gprx {

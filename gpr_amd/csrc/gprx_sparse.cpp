@@ -1,5 +1,6 @@
 // gprx_sparse.cpp — the sparse GP: its streamed normal equations, fit and log marginal likelihood.
 #include "gprx_model.h"
+#include "sparse_plan.h"
 
 namespace gprx {
 
@@ -40,11 +41,16 @@ struct SparseNE {
     const KCanon<T>* kdev = nullptr;  // ... for the MFMA builds (set when mma)
     const T* pX = nullptr;  // the dense rows and labels in HBM: the caller's device memory, or dX / dY
     const T* pY = nullptr;
-    // the streamed block dA (ld x acols): columns from dA_zero on are known to hold zeros (its
-    // layout last zeroed whole for dA_p, dA_ld, dA_cols); a chunk zeroes only the columns between
-    // its own end and dA_zero, instead of the whole 4.6 GB block (two memsets of it per C5 fit)
-    void* dA_p = nullptr;
-    int64_t dA_ld = 0, dA_cols = 0, dA_zero = 0;
+    // the streamed block dA (column-major, ld x acols) keeps what the last call's chunks stored.  The
+    // rank-k accumulation reads rows [0, Mp) (and the label rows) x the split-K slices' columns,
+    // while a chunk's build stores only rows [0, M) x columns [0, nc).  Invariant, before each
+    // accumulation: every element it reads is either stored by this chunk or zero.  blk records
+    // what can be non-zero (columns below blk.zero, Kmn rows below blk.rows), and sparse_clear_plan
+    // (sparse_plan.cpp) turns it into the rectangles a chunk must zero first: the columns an
+    // earlier, longer chunk left past this one's end, the rows an earlier call with more inducing
+    // points left past this one's M, the whole block only when its layout changes (not the whole
+    // 4.6 GB block per chunk: that was two memsets of it per C5 fit)
+    SparseBlock blk;
 };
 
 // The sparse fit's device state lives in the context between calls (its buffers -- the
@@ -137,26 +143,23 @@ static void sparse_normal_eq(gprx_ctx* ctx, SparseNE<T>& st, const gprx_kernel_d
     GPRX_HIP(hipMemsetAsync(dS.p, 0, sizeof(T) * sstride * P, s));
     const int64_t acols = chunk + 16 * 16;  // slack: the P <= 16 split-K slices may overhang ncp (zeros)
     dA.ensure(sizeof(T) * ld * acols);
-    if (dA.p != st.dA_p || st.dA_ld != ld || st.dA_cols != acols) {  // a new block layout: zero it whole
-        GPRX_HIP(hipMemsetAsync(dA.p, 0, sizeof(T) * ld * acols, s));
-        st.dA_p = dA.p;
-        st.dA_ld = ld;
-        st.dA_cols = acols;
-        st.dA_zero = 0;
-    }
     const T is2 = T(1) / (T(sigma) * T(sigma));  // inverse_sigma2 in T (:285)
     st.is2 = is2;
     DevBuf dKY;
     if (fused) dKY.ensure(sizeof(T) * (chunk128 / GT) * Mp);
     for (int64_t off = 0; off < n; off += chunk) {
         const int64_t nc = std::min(chunk, n - off), ncp = round_up(nc, 16);
-        // columns [nc, acols) must be zero for this chunk's products (the split-K slices overhang
-        // the data): zero what an earlier, longer chunk left there; this chunk dirties [0, ncp)
-        if (st.dA_zero > nc) {
-            GPRX_HIP(hipMemsetAsync(dA.as<T>() + nc * ld, 0, sizeof(T) * ld * (st.dA_zero - nc), s));
-            st.dA_zero = nc;
+        // what this chunk's products read beside its own stores must be zero (SparseNE::blk)
+        ClearRect rect[SPARSE_CLEAR_MAX];
+        const int nrect = sparse_clear_plan(st.blk, (int64_t)(uintptr_t)dA.p, ld, acols, Mp, M, nc, rect);
+        for (int q = 0; q < nrect; q++) {
+            const ClearRect& r = rect[q];
+            T* p = dA.as<T>() + r.col0 * ld + r.row0;
+            if (r.nrows == ld)  // whole columns: contiguous
+                GPRX_HIP(hipMemsetAsync(p, 0, sizeof(T) * ld * r.ncols, s));
+            else
+                GPRX_HIP(hipMemset2DAsync(p, sizeof(T) * ld, 0, sizeof(T) * r.nrows, r.ncols, s));
         }
-        st.dA_zero = std::max(st.dA_zero, ncp);
         if (mma) {
             const int64_t nc128 = round_up(nc, GT);
             launch_pair_features<T>(K, st.pX + off * d, nc, d, dXm.as<T>(), true, dFV.as<T>(), nc128, s,

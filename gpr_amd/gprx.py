@@ -211,6 +211,8 @@ def lib():
         L.gprx_dev_panel_trace.argtypes = [ctypes.c_void_p, ctypes.c_int64]
         L.gprx_dev_normals.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint64, ctypes.c_int64, ctypes.c_void_p]
         L.gprx_dev_sample_phases.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double)]
+        L.gprx_dev_sparse_clear_plan.restype = ctypes.c_int32
+        L.gprx_dev_sparse_clear_plan.argtypes = [ctypes.c_void_p] + [ctypes.c_int64] * 6 + [ctypes.c_void_p]
         _lib = L
     return _lib
 

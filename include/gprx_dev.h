@@ -135,6 +135,14 @@ gprx_status gprx_dev_normals(gprx_ctx* ctx, gprx_dtype dtype, uint64_t seed, int
  * on (gprx_ctx_set_stats; zeros otherwise): ms[0] cross build K(Xq, X), [1] row solve, [2] K(Xq, Xq)
  * and the rank update, [3] factorisation (every attempt), [4] normals and their staging, [5] transform. */
 gprx_status gprx_dev_sample_phases(gprx_model* model, double* ms);
+/* Host-only: the clearing plan of the sparse GP's streamed block (sparse_plan.cpp), one chunk of a
+ * call.  state: 6 int64 {allocation id, ld, columns, Mp, zero, rows} kept by the caller between
+ * calls (all zeros: nothing known) and advanced to the state after the chunk; (id, ld, cols, Mp):
+ * the block this call uses; M inducing points; nc dense rows in the chunk.  Writes the rectangles
+ * to zero before the chunk's build, 4 int64 each {row0, rows, col0, columns}, at most 3, into
+ * rects; returns their count, -1 on bad arguments.  Needs no device. */
+int32_t gprx_dev_sparse_clear_plan(int64_t* state, int64_t id, int64_t ld, int64_t cols, int64_t Mp, int64_t M,
+                                   int64_t nc, int64_t* rects);
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,14 @@ def case_sparse(ctx, vctx):
     return out
 
 
+def case_sparse_reuse(ctx, vctx):
+    """The sparse state reused: fewer inducing points on the same padded layout and back (MFMA and
+    VALU builds, below one tile), label rows <-> the fused K Y (tests/sparse_reuse_ref.py)."""
+    from tests import sparse_reuse_ref as R
+    return {f"sparse_reuse/{k}": v
+            for k, v in R.collect(ctx, ("shrink_g", "shrink_gw", "shrink_small", "labels")).items()}
+
+
 # ---------------------------------------------------------------------------------------
 # leave-one-out in fp32 (the f64 cases run poisoned in test_gpu_loo.py)
 # ---------------------------------------------------------------------------------------
@@ -200,6 +208,7 @@ CASES = {
     "normals": case_normals,
     "posterior_and_sample": case_posterior_and_sample,
     "sparse": case_sparse,
+    "sparse_reuse": case_sparse_reuse,
     "loo_f32": case_loo_f32,
     "sharded": case_sharded,
 }

@@ -35,6 +35,18 @@ def test_abi_version():
     assert gpr_amd.lib().gprx_abi_version() == 2
 
 
+def test_sparse_clear_plan_hook_needs_no_device():
+    """gprx_dev_sparse_clear_plan (the sparse GP's clearing plan, tests/test_sparse_reuse_cpu.py) is
+    bound and answers on a GPU-less host: -1 on bad arguments, a first chunk clears the block."""
+    import numpy as np
+    L = gpr_amd.lib()
+    state, rects = np.zeros(6, np.int64), np.zeros(12, np.int64)
+    assert L.gprx_dev_sparse_clear_plan(state.ctypes.data, 1, 256, 896, 128, 129, 600, rects.ctypes.data) == -1
+    assert L.gprx_dev_sparse_clear_plan(None, 1, 256, 896, 128, 100, 600, rects.ctypes.data) == -1
+    assert L.gprx_dev_sparse_clear_plan(state.ctypes.data, 1, 256, 896, 128, 100, 600, rects.ctypes.data) == 1
+    assert list(rects[:4]) == [0, 256, 0, 896] and list(state) == [1, 256, 896, 128, 608, 100]
+
+
 def test_struct_layouts_match_header():
     # gprx_knode: int32 op, int32 pad, double p[3] -> 32 bytes; desc: 8 + 32*32
     assert ctypes.sizeof(gprx.KNode) == 32

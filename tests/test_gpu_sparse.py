@@ -278,27 +278,29 @@ def test_sparse_reference_gradient_config(ctx):
 
 def test_sparse_streamed_block_reuse(monkeypatch):
     """The streamed Kmn block lives in the context between fits and only the columns a longer
-    chunk left behind are re-zeroed (gprx_sparse.cpp SparseNE::dA_zero): fits of different lengths
-    (a ragged last chunk, then whole chunks, then ragged again) on one context give the same bits
-    as the same fits on fresh contexts."""
+    chunk left behind, and the rows that a fit with more inducing points left behind, are re-zeroed
+    (gprx_sparse.cpp SparseNE::blk, sparse_plan.cpp): fits of different lengths (a ragged last
+    chunk, then whole chunks, then ragged again) and of fewer inducing points on the same padded
+    layout (M = 290 after M = 300) on one context give the same bits as the same fits on fresh
+    contexts."""
     import gpr_amd
     monkeypatch.setenv("GPRX_SPARSE_CHUNK", "2048")
     ks = CASES[0][0]
-    shapes = [(5000, 11), (4096, 12), (3000, 13), (5000, 11)]
+    shapes = [(5000, 11, 300), (5000, 14, 290), (4096, 12, 300), (3000, 13, 300), (5000, 11, 300)]
     shared = gpr_amd.Context(0)
     try:
         got = []
-        for n, seed in shapes:
+        for n, seed, M in shapes:
             X, Y = make_data(n, 8, 1)
             X = X + 1e-3 * seed
-            Xm = X[:: n // 300][:300].copy()
+            Xm = X[:: n // M][:M].copy()
             got.append(shared.sparse_fit(ks, X, Y, Xm, 0.3, 1e-3, np.float64))
     finally:
         shared.close()
-    for (n, seed), g in zip(shapes, got):
+    for (n, seed, M), g in zip(shapes, got):
         X, Y = make_data(n, 8, 1)
         X = X + 1e-3 * seed
-        Xm = X[:: n // 300][:300].copy()
+        Xm = X[:: n // M][:M].copy()
         fresh = gpr_amd.Context(0)
         try:
             ref = fresh.sparse_fit(ks, X, Y, Xm, 0.3, 1e-3, np.float64)
